@@ -16,8 +16,17 @@ The total work per step is fixed as N grows, so scaling is "strong".
     torchrun --nproc-per-node 8 --master-addr 127.0.0.1 bench.py --gpus 8   # same, launched by torchrun
     python bench.py --model swav            # BASELINE config 3 (collaborative SwAV ResNet-50), same contract
 
-The default single-GPU run also measures BASELINE config 3 in a child process (after the timed ALBERT
-region) and reports it under the ``swav`` key of the same JSON line (``--swav 0`` turns that off).
+    python bench.py --full                  # the headline, then everything else this script measures
+    python bench.py --dump-outputs DIR      # also write what the last timed step computed as DIR/*.npy
+
+A plain run does only what the headline figure needs: set-up, warm-up, the timed steps, the output
+dump if asked for, the JSON line.  With ``--full`` the single-GPU run also measures BASELINE config 3
+in a child process (after the timed ALBERT region) and reports it under the ``swav`` key of the same
+JSON line (``--swav 0`` turns that off).
+
+The synthetic data stream of peer i is seeded from ``--data_seed`` + i and the weights from the fixed
+model seed, so two runs with the same arguments train on identical inputs and ``--dump-outputs`` of
+two builds can be compared array for array.
 
 Peers are independent processes, one per GPU, as in the reference's fleet (each AWS worker runs its
 own run_trainer, albert/AWS_runner.ipynb:293-297).  Without a launcher (no WORLD_SIZE in the
@@ -93,8 +102,20 @@ def parse():
     ap.add_argument("--allow_shared_device", action="store_true",
                     help="let several peers share one GPU (protocol emulation on a small box); the JSON line "
                          "reports physical_gpus < n_gpus.  Without it, more peers than visible GPUs is an error")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else this script measures (today: the SwAV child "
+                         "run, see --swav); off by default, so a plain run only sets up, warms up, times its steps "
+                         "and prints the JSON line")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step left its caller as DIR/<name>.npy "
+                         "(rank 0): params.npy, the fp32 master parameters after that step's optimizer update (a fixed "
+                         "seeded sample of them when they exceed the size budget), and loss.npy, that step's mean "
+                         "micro-batch loss (float64)")
+    ap.add_argument("--data_seed", type=int, default=1234,
+                    help="seed of the synthetic data stream (peer i uses data_seed + i): the same arguments give the "
+                         "same inputs in every run")
     ap.add_argument("--swav", type=int, default=1,
-                    help="with the default single-GPU ALBERT run: also measure BASELINE config 3 (--model swav) in a "
+                    help="with --full on the single-GPU ALBERT run: also measure BASELINE config 3 (--model swav) in a "
                          "fresh child process after the timed region (this process frees its memory first), and report it under the "
                          "'swav' key (the headline keys are unchanged; a child failure only sets swav.error).  0: off")
     ap.add_argument("--swav_steps", type=int, default=3, help="timed collaborative steps of the SwAV child run")
@@ -185,6 +206,46 @@ def _swav_child(args) -> dict:
     keep = ("metric", "value", "unit", "vs_baseline", "ms_per_step", "steps", "warmup", "config", "data_plane",
             "ema_samples_per_s_sum", "first_microstep_s")
     return dict({k: out.get(k) for k in keep}, wall_s=round(time.perf_counter() - t0, 1), cmd=" ".join(cmd[1:]))
+
+
+def _seed_data(peer, seed: int):
+    """A peer seeds its synthetic data from its public key, which is drawn afresh in every process;
+    the benchmark replaces that with ``seed`` so that every run with the same arguments sees the same
+    batches (same generator, same distribution — only the seed's origin differs)."""
+    from dedloc_amd.data.multicrop import StreamPrefetcher, SyntheticMultiCropStream
+
+    data = peer.data
+    src = data.source if isinstance(data, StreamPrefetcher) else data
+    if isinstance(src, SyntheticMultiCropStream):  # its image pool is drawn from the seed too: build it anew
+        new = SyntheticMultiCropStream(src.batch_size, src.device, seed=seed, pool_size=src.pool.shape[0],
+                                       image_size=src.pool.shape[-1], augment=src.augment, out_dtype=src.out_dtype)
+        peer.data = StreamPrefetcher(new, data.device) if src is not data else new
+    else:
+        src.gen.manual_seed(seed)
+
+
+DUMP_BUDGET_BYTES = 32 << 20  # per array; the whole dump stays well under 64 MB
+
+
+def _dump_outputs(peer, out_dir: str):
+    """What the last timed step left its caller, as float32/float64 ``.npy`` files: the fp32 master
+    parameters after the step's optimizer update (``params.npy``; when they exceed the budget, the
+    elements at a fixed seeded set of sorted indices, the same in every run) and the step's mean
+    micro-batch loss (``loss.npy``, float64, one element)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    flat = peer.flat if hasattr(peer, "flat") else peer.model.flat
+    params = flat.fp32.detach()
+    keep = DUMP_BUDGET_BYTES // 4
+    if params.numel() > keep:
+        idx = torch.randperm(params.numel(), generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        params = params[idx.to(params.device)]
+    np.save(os.path.join(out_dir, "params.npy"), params.float().cpu().numpy())
+    if not peer.metrics_log:  # no global step was taken
+        return
+    rec = peer.metrics_log[-1]  # the last global step's record (the caller flushed the metrics)
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([rec["loss"] / max(1, rec["mini_steps"])], dtype=np.float64))
 
 
 def _protocol_breakdown(gathered, keys):
@@ -313,7 +374,7 @@ def main():
         sys.exit(_self_launch(args))
     # the SwAV child run (BASELINE config 3) happens AFTER the timed ALBERT region, once this process
     # has released its GPU memory, so the headline is measured on a cool, idle device
-    want_swav = (args.swav and args.model == "albert" and args.impl == "dedloc" and not args.cpu_test
+    want_swav = (args.full and args.swav and args.model == "albert" and args.impl == "dedloc" and not args.cpu_test
                  and args.gpus == 1 and "WORLD_SIZE" not in os.environ and torch.cuda.device_count() > 0)
     logging.basicConfig(level=logging.INFO if args.verbose else logging.WARNING,
                         format="%(asctime)s %(levelname)s %(name)s: %(message)s")
@@ -344,6 +405,7 @@ def main():
         peer, bs, describe = _swav_peer(args, rank, dev, ep[0])
     else:
         peer, bs, describe = _albert_peer(args, rank, world, dev, ep[0])
+    _seed_data(peer, args.data_seed + rank)
     co = peer.collab_opt
 
     def run_until(step):
@@ -411,6 +473,8 @@ def main():
                 # successful timed-region rounds per peer: over RCCL / over gloo or mixed groups
                 "rounds_rccl": [int(g[n0 + 5]) for g in gathered], "rounds_other": [int(g[n0 + 6]) for g in gathered]}
     fallback = rccl_fallback(dev.type, world, physical, per_peer["rounds_rccl"], per_peer["rounds_other"])
+    if rank == 0 and args.dump_outputs:
+        _dump_outputs(peer, args.dump_outputs)
     if rank == 0:
         value = total_samples / max_dt
         out = dict(describe(value, world), n_gpus=world, steps=args.steps, warmup=args.warmup,

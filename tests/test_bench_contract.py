@@ -80,6 +80,39 @@ def test_bench_self_launches_peers_without_torchrun(tmp_path):
     assert out["data_plane"] == "gloo"
 
 
+@pytest.mark.timeout(300)
+def test_bench_dump_outputs_repeat_on_identical_inputs(tmp_path):
+    """`--dump-outputs DIR` writes the last timed step's parameters and loss as float .npy files, and
+    two runs with the same arguments see the same inputs: on the CPU (one thread, no atomics) the
+    dumps are then equal bit for bit.  A plain run reports nothing but the headline (no `swav` key)."""
+    import numpy as np
+
+    from dedloc_amd.models.albert import AlbertConfig
+
+    cfg = tmp_path / "cfg"
+    AlbertConfig.tiny(num_hidden_layers=2, max_position_embeddings=64).save_pretrained(str(cfg))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env.update(OMP_NUM_THREADS="1", PYTHONPATH=ROOT)
+    dumps = []
+    for run in range(2):
+        out_dir = tmp_path / f"dump{run}"
+        cmd = [sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--cpu_test", str(cfg),
+               "--micro_batch", "2", "--seq_len", "64", "--target_batch_size", "8", "--dump-outputs", str(out_dir)]
+        r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=140, env=env)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        out = json.loads(lines[0])
+        assert KEYS <= set(out) and out["steps"] == 2 and out["ms_per_step"] > 0 and "swav" not in out
+        assert sorted(p.name for p in out_dir.iterdir()) == ["loss.npy", "params.npy"]
+        dumps.append({p.stem: np.load(p) for p in out_dir.iterdir()})
+    a, b = dumps
+    assert a["params"].dtype == np.float32 and a["loss"].dtype == np.float64 and a["loss"].shape == (1,)
+    assert a["params"].size > 1000 and np.isfinite(a["params"]).all() and np.isfinite(a["loss"]).all()
+    assert a["params"].std() > 0
+    assert np.array_equal(a["params"], b["params"]) and np.array_equal(a["loss"], b["loss"])
+
+
 @pytest.mark.gpu
 @pytest.mark.timeout(120)
 def test_bench_refuses_more_peers_than_gpus():

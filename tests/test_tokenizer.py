@@ -1,7 +1,8 @@
 """sahajBERT tokenizer: Bengali normalisation, the Unigram training recipe with the
 reference README's post-training edits, the transformers wrapper, and tokenization parity with the
-reference's shipped ``sahajbert/tokenizer/data/tokenizer.json`` (read as JSON; skipped when the
-reference tree is absent, e.g. on the GPU box)."""
+reference's shipped ``sahajbert/tokenizer/data/tokenizer.json`` (a copy of that data file is kept
+under tests/golden/)."""
+import gzip
 import json
 import os
 import random
@@ -14,7 +15,8 @@ from dedloc_amd.data.tokenizer import (SPECIAL_TOKENS, AlbertBengaliTokenizerFas
                                        train_tokenizer)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF_TOKENIZER = "/root/reference/sahajbert/tokenizer/data/tokenizer.json"
+# the reference's shipped sahajbert/tokenizer/data/tokenizer.json, byte for byte (gzip: 1.7 MB unpacked)
+REF_TOKENIZER_GZ = os.path.join(ROOT, "tests", "golden", "sahajbert_tokenizer.json.gz")
 LETTERS = "অআইঈউএওকখগঘচছজঝটঠডঢতথদধনপফবভমযরলশষসহড়য়"
 SIGNS = "ািীুূেৈোৌং"
 
@@ -61,12 +63,14 @@ def test_train_and_wrap(tmp_path):
     assert set(enc["token_type_ids"][:first_sep + 1]) == {0} and set(enc["token_type_ids"][first_sep + 1:]) == {1}
 
 
-@pytest.mark.skipif(not os.path.exists(REF_TOKENIZER), reason="reference tokenizer artifact not present")
-def test_pipeline_parity_with_reference_artifact():
+def test_pipeline_parity_with_reference_artifact(tmp_path):
     """Our normalizer / pre-tokenizer / template around the reference's trained Unigram model encode
     exactly like the reference's tokenizer.json."""
     from tokenizers import Tokenizer
 
+    REF_TOKENIZER = str(tmp_path / "tokenizer.json")
+    with gzip.open(REF_TOKENIZER_GZ, "rb") as src, open(REF_TOKENIZER, "wb") as dst:
+        dst.write(src.read())
     ref = Tokenizer.from_file(REF_TOKENIZER)
     ours = bengali_pipeline(model=Tokenizer.from_file(REF_TOKENIZER).model)
     ours.add_special_tokens(list(SPECIAL_TOKENS))
