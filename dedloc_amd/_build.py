@@ -115,10 +115,14 @@ def build(verbose: bool = False, jobs: int | None = None) -> str:
 
 _OBJS: list = []  # the kernel library's objects, in link order (filled by build)
 HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-munsafe-fp-atomics"]
-# per-file extra flags (none at present: -fno-slp-vectorize on attention.hip, which keeps the softmax
+# per-file extra flags (not used: -fno-slp-vectorize on attention.hip, which keeps the softmax
 # f32 arithmetic out of v_pk_*_f32, measured 2.5% slower in the backward and equal in the forward —
-# profiles/r4_ab_attention_no_slp.jsonl)
-FILE_FLAGS: dict = {}
+# profiles/r4_ab_attention_no_slp.jsonl).
+# comm_q8.hip: contraction inside one expression only.  A decoded value code * scale must be the
+# rounded product wherever it is used: with =fast the compiler fuses the multiply into some of the
+# later subtractions (avg - v_k), which then see the exact product, and identical rows no longer
+# give zero deltas.
+FILE_FLAGS: dict = {"comm_q8.hip": ["-ffp-contract=on"]}
 
 
 def _link(objs, out, tlib, verbose):

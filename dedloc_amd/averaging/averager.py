@@ -5,7 +5,8 @@ In-process design (no helper processes, no host staging of the averaged tensors)
     ``target_group_size``, when every live peer of the collaboration has joined, or when the
     ``averaging_expiration`` window of its first member ends;
   * the data plane is the butterfly all-reduce (``allreduce.butterfly_allreduce``) with LP-balanced
-    parts and FLOAT16/BFLOAT16 wire compression, on a communicator the group's members build
+    parts and FLOAT16/BFLOAT16/BLOCKWISE_8BIT wire compression (one codec per averaged tensor; the
+    members of a round must announce the same codecs), on a communicator the group's members build
     through the DHT (``parallel.GroupCommunicators``: RCCL between GPU peers, gloo when a CPU peer
     is a member).  Nothing depends on a launch-time world, so any process that can reach the DHT
     — a late volunteer, a respawned spot instance — averages in the next round it joins.  A failed
@@ -32,7 +33,8 @@ import torch
 from ..dht import DHT, get_dht_time, parse_endpoint
 from ..parallel import comm as _comm
 from ..parallel.comm import CommError, GroupCommunicators, RcclGroupComm, pairwise_rccl, routable_host
-from .allreduce import GroupSpec, WIRE_DTYPES, butterfly_allreduce
+from .allreduce import (GroupSpec, butterfly_allreduce, compression_signature, resolve_compression,
+                        wire_bytes_per_value)
 from .load_balancing import load_balance_peers
 
 logger = logging.getLogger(__name__)
@@ -248,9 +250,9 @@ class DecentralizedAverager:
         self.dht, self.prefix, self.peer_id = dht, prefix, bytes(peer_id)
         self.target_group_size, self.min_group_size = target_group_size, min_group_size
         self.averaging_expiration, self.averaging_timeout = averaging_expiration, averaging_timeout
-        if compression not in WIRE_DTYPES:
-            raise ValueError(f"unknown compression {compression}; expected one of {sorted(WIRE_DTYPES)}")
-        self.compression = compression
+        # a codec name, or one per averaged tensor (validated here: an unknown name raises ValueError)
+        resolve_compression(compression, len(self.averaged_tensors) if not isinstance(compression, str) else 1)
+        self.compression = compression if isinstance(compression, str) else list(compression)
         self.throughput = throughput
         self.client_mode, self.auxiliary = client_mode, auxiliary
         self.allow_state_sharing = allow_state_sharing and not auxiliary
@@ -293,11 +295,17 @@ class DecentralizedAverager:
         return [(cls.XGMI_MBPS if (b is None or b > 0) else 0.0) if p in on_rccl
                 else (cls.DEFAULT_HOST_MBPS if b is None else b) for b, p in zip(bws, pids)]
 
-    def _info(self, weight: Optional[float], gather: Optional[Dict[str, Any]]) -> Dict:
+    def _info(self, weight: Optional[float], gather: Optional[Dict[str, Any]],
+              codecs: Optional[Sequence[str]] = None) -> Dict:
         bw = 0.0 if self.client_mode else self.throughput  # None: not declared
         info = {"bandwidth": bw, "weight": weight, "aux": self.auxiliary, "gather": gather or {}}
+        if codecs is not None:  # this round's codec signature: every member must announce the same one
+            info["compression"] = compression_signature(codecs)
         info.update(self.comms.announce())
         return info
+
+    def _codecs(self, compression, tensors: Sequence[torch.Tensor]) -> List[str]:
+        return resolve_compression(self.compression if compression is None else compression, len(tensors))
 
     def _join(self, info: Dict, expected_group_size: int, key_suffix: str):
         window = self.averaging_expiration
@@ -315,7 +323,8 @@ class DecentralizedAverager:
         looking for group in advance"), so the group forms while that micro-step computes.  The
         weight is not known yet and need not be: weights travel with the data (allreduce.py)."""
         fut: Future = Future()
-        info = self._info(None if not self.auxiliary else 0.0, gather)
+        # a prejoined round averages the averager's own tensors with its own codecs
+        info = self._info(None if not self.auxiliary else 0.0, gather, self._codecs(None, self.averaged_tensors))
 
         def run():
             try:
@@ -329,14 +338,16 @@ class DecentralizedAverager:
     def step(self, weight=1.0, timeout: Optional[float] = None, expected_group_size: int = 0,
              gather: Optional[Dict[str, Any]] = None, tensors: Optional[Sequence[torch.Tensor]] = None,
              sources: Optional[Sequence[torch.Tensor]] = None, key_suffix: str = "",
-             prejoined: Optional[Future] = None) -> Optional[Dict]:
+             prejoined: Optional[Future] = None, compression=None) -> Optional[Dict]:
         """Matchmake and average.  Returns {"group_id", "size", "gathered"} or None on failure.
 
-        ``tensors`` overrides the averaged set for this round (e.g. gradients only), ``sources`` packs
+        ``tensors`` overrides the averaged set for this round (e.g. gradients only) and
+        ``compression`` (a name or one per tensor) the codecs for it, ``sources`` packs
         snapshots instead of the live tensors, ``key_suffix`` selects an independent matchmaking key
         (so a delayed parameter round never mixes with a gradient round), ``prejoined`` is a
         ``prejoin`` future whose group this round uses (a fresh matchmaking if it failed)."""
         tensors = list(tensors) if tensors is not None else self.averaged_tensors
+        codecs = self._codecs(compression, tensors)
         # a device-scalar weight (CollaborativeOptimizer's finite-sample count) travels as is
         weight = 0.0 if self.auxiliary else (weight if isinstance(weight, torch.Tensor) else float(weight))
         t_wait = time.perf_counter()
@@ -351,7 +362,7 @@ class DecentralizedAverager:
                 res = None
         if res is None:
             try:
-                res = self._join(self._info(weight if not isinstance(weight, torch.Tensor) else None, gather),
+                res = self._join(self._info(weight if not isinstance(weight, torch.Tensor) else None, gather, codecs),
                                  expected_group_size, key_suffix)
             except Exception as e:  # noqa: BLE001
                 logger.warning(f"matchmaking failed: {e}")
@@ -364,6 +375,16 @@ class DecentralizedAverager:
         infos = [m[1] for m in members]
         pids = [bytes(m[0]) for m in members]
         my_index = pids.index(self.peer_id)
+        # members that would pack different wire formats cannot average: fail the round now instead
+        # of posting transfers of different sizes that only end at the timeout (a member that
+        # announces no signature counts as compatible)
+        signature = compression_signature(codecs)
+        for pid, info in zip(pids, infos):
+            theirs = info.get("compression")
+            if theirs is not None and theirs != signature:
+                logger.warning(f"averaging round failed: this peer compresses with {signature}, peer {pid!r} "
+                               f"with {theirs}")
+                return None
         V = sum(t.numel() for t in tensors)
         hybrid = GroupCommunicators.group_backend(members) == "hybrid"
         bws = self.group_bandwidths(infos, pids, set(GroupCommunicators.rccl_members(members)) if hybrid else None)
@@ -379,7 +400,7 @@ class DecentralizedAverager:
                              weights=[weight if k == my_index else 0.0 for k in range(len(pids))],
                              contributes=[not i["aux"] for i in infos], my_index=my_index)
             with self.lock_averaged_tensors:
-                butterfly_allreduce(tensors, spec, self.compression, comm=comm,
+                butterfly_allreduce(tensors, spec, codecs, comm=comm,
                                     timeout=max(1e-3, deadline - time.monotonic()), sources=sources)
         except (CommError, RuntimeError) as e:
             # the communicator may still hold posted operations: it is aborted and forgotten, so the
@@ -392,7 +413,7 @@ class DecentralizedAverager:
         if self.emulate_transfer_delay and bw is not None and bw > 0:  # emulate the volunteer's link (AWS_runner wondershaper caps)
             from ..emulation.heterogeneity import emulated_transfer_seconds
 
-            wire_bytes = torch.empty(0, dtype=WIRE_DTYPES[self.compression]).element_size()
+            wire_bytes = wire_bytes_per_value(codecs, [t.numel() for t in tensors])
             want = 2 * emulated_transfer_seconds(V, wire_bytes, len(members), parts[my_index] / max(1, V), bw)
             spent = time.perf_counter() - t0
             if want > spent:

@@ -37,7 +37,8 @@ class CollaborativeOptimizerArguments:
     client_mode: bool = field(default=False, metadata={"help": "If True, runs training without incoming connections"})
     batch_size_lead: int = field(default=0, metadata={"help": "Optional: begin looking for group in advance, this many samples before target_batch_size"})
     bandwidth: float = field(default=100.0, metadata={"help": "Available network bandwidth, in mbps (used for load balancing in all-reduce)"})
-    compression: str = field(default="FLOAT16", metadata={"help": "Use this compression when averaging parameters/gradients (NONE, FLOAT16, BFLOAT16)"})
+    compression: str = field(default="FLOAT16", metadata={"help": "Use this compression when averaging gradients, and parameters unless --state_averaging_compression is given (NONE, FLOAT16, BFLOAT16, BLOCKWISE_8BIT)"})
+    state_averaging_compression: Optional[str] = field(default=None, metadata={"help": "Use this compression when averaging parameters (default: the same as --compression); recommended with --compression BLOCKWISE_8BIT: FLOAT16"})
 
 
 @dataclass

@@ -55,6 +55,7 @@ class CheckpointHandler:
         av = asdict(averager_args)
         self.collaborative_optimizer = CollaborativeOptimizer(
             opt=opt, dht=dht, prefix=coordinator_args.experiment_prefix, compression_type=ca.compression,
+            state_averaging_compression=ca.state_averaging_compression,
             throughput=ca.bandwidth, target_batch_size=ca.target_batch_size - ca.batch_size_lead,
             client_mode=ca.client_mode, verbose=True, start=False, allow_state_sharing=False,
             peer_id=local_public_key + b"#coordinator", **av)

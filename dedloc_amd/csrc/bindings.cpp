@@ -272,6 +272,39 @@ void unpack(const at::Tensor& src, at::Tensor dst, const c10::optional<at::Tenso
   check(dl_unpack(src.data_ptr(), dtype_code(src), f32(dst), sp, add ? 1 : 0, dst.numel(), cur_stream(dst)), "unpack");
 }
 
+// BLOCKWISE_8BIT wire codec: an encoded segment of n values is a 16-byte aligned uint8 [q8_bytes(n)]
+inline void expect_q8(const at::Tensor& t, int64_t rows, int64_t n, const char* name) {
+  expect(t, at::kByte, name);
+  TORCH_CHECK(n >= 1, name, ": a segment holds at least one value");
+  TORCH_CHECK(t.numel() == rows * (int64_t)dl_q8_bytes((size_t)n), name, " must hold ", rows, " x q8_bytes(", n,
+              ") = ", rows * (int64_t)dl_q8_bytes((size_t)n), " bytes, has ", t.numel());
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, name, " must be 16-byte aligned");
+}
+
+void pack_q8(const at::Tensor& src, at::Tensor dst) {
+  expect(src, at::kFloat, "src");
+  expect_q8(dst, 1, src.numel(), "dst");
+  check(dl_pack_q8(f32(src), dst.data_ptr(), src.numel(), cur_stream(src)), "pack_q8");
+}
+
+void reduce_delta_q8(const at::Tensor& parts, const at::Tensor& weights, at::Tensor deltas, int64_t n) {
+  TORCH_CHECK(parts.dim() == 2 && deltas.dim() == 2 && deltas.sizes() == parts.sizes(), "deltas must match parts [k, bytes]");
+  const int64_t nparts = parts.size(0);
+  TORCH_CHECK(nparts >= 1 && nparts <= 64, "reduce_delta_q8: 1 to 64 senders");
+  expect_q8(parts, nparts, n, "parts");
+  expect_q8(deltas, nparts, n, "deltas");
+  expect(weights, at::kFloat, "weights");
+  TORCH_CHECK(weights.numel() == nparts, "one weight per part");
+  check(dl_reduce_delta_q8(parts.data_ptr(), deltas.data_ptr(), (int)nparts, f32(weights), (size_t)n, cur_stream(parts)),
+        "reduce_delta_q8");
+}
+
+void unpack_q8(const at::Tensor& src, at::Tensor dst, bool add) {
+  expect(dst, at::kFloat, "dst");
+  expect_q8(src, 1, dst.numel(), "src");
+  check(dl_unpack_q8(src.data_ptr(), f32(dst), add ? 1 : 0, dst.numel(), cur_stream(dst)), "unpack_q8");
+}
+
 // ------------------------------------------------------------------ embeddings / loss
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> embed_ln_fwd(
     const at::Tensor& ids, const c10::optional<at::Tensor>& tt, const at::Tensor& wemb, const at::Tensor& pemb,
@@ -1542,6 +1575,9 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("reduce_parts", &reduce_parts);
   m.impl("unpack", &unpack);
   m.impl("reduce_delta", &reduce_delta);
+  m.impl("pack_q8", &pack_q8);
+  m.impl("reduce_delta_q8", &reduce_delta_q8);
+  m.impl("unpack_q8", &unpack_q8);
   m.impl("embed_ln_fwd", &embed_ln_fwd);
   m.impl("embed_bwd", &embed_bwd);
   m.impl("xent_fwd_bwd", &xent_fwd_bwd);

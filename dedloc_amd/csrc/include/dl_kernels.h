@@ -57,6 +57,14 @@ int dl_unpack(const void* src, int src_dt, float* dst, const float* snap, int ad
 int dl_reduce_delta(const void* parts, void* deltas, int dt, size_t part_stride, int nparts, const float* weights,
                     size_t n, hipStream_t st);
 
+// comm_q8.hip: the BLOCKWISE_8BIT wire codec (encoded buffers are 16-byte aligned; the fp32 side may
+// be only 4-byte aligned)
+size_t dl_q8_bytes(size_t n);  // bytes of one encoded segment of n values
+int dl_pack_q8(const float* src, void* dst, size_t n, hipStream_t st);
+int dl_unpack_q8(const void* src, float* dst, int add, size_t n, hipStream_t st);
+// parts, deltas: [nparts, dl_q8_bytes(n)] bytes
+int dl_reduce_delta_q8(const void* parts, void* deltas, int nparts, const float* weights, size_t n, hipStream_t st);
+
 // embedding.hip
 int dl_embed_ln_fwd(const long* ids, const long* tt, const float* wemb, const float* pemb, const float* temb,
                     const float* gamma, const float* beta, bf16_t* y, bf16_t* s_out, float* mean, float* rstd, int T,

@@ -36,6 +36,9 @@ _SCHEMAS = [
     "reduce_parts(Tensor parts, int nparts, Tensor(a!) out, float inv_total) -> ()",
     "unpack(Tensor src, Tensor(a!) dst, Tensor? snap, bool add=False) -> ()",
     "reduce_delta(Tensor parts, Tensor weights, Tensor(a!) deltas) -> ()",
+    "pack_q8(Tensor src, Tensor(a!) dst) -> ()",
+    "reduce_delta_q8(Tensor parts, Tensor weights, Tensor(a!) deltas, int n) -> ()",
+    "unpack_q8(Tensor src, Tensor(a!) dst, bool add=False) -> ()",
     "embed_ln_fwd(Tensor ids, Tensor? tt, Tensor wemb, Tensor pemb, Tensor temb, Tensor gamma, Tensor beta, int S, float eps) -> (Tensor, Tensor, Tensor, Tensor)",
     "embed_bwd(Tensor ds, Tensor ids, Tensor? tt, Tensor(a!) dwemb, Tensor(b!) dpemb, Tensor(c!) dtemb, int S) -> ()",
     "xent_fwd_bwd(Tensor logits, Tensor labels, bool inplace, int ignore_index) -> (Tensor, Tensor)",
@@ -343,6 +346,87 @@ def _unpack_cpu(src, dst, snap, add=False):
         dst.copy_(src.float())
     else:
         dst.add_(src.float() - snap)
+
+
+# BLOCKWISE_8BIT wire codec (csrc/kernels/comm_q8.hip): blocks of Q8_BLOCK values counted from the
+# segment's start, scale = max|x| / 127 per block, code = clamp(rint(x / scale), -127, 127).  One
+# encoded segment is uint8 [q8_bytes(n)]: the fp32 scales at byte 0, the int8 codes from
+# round_up(4 nb, 16), padding bytes 0.  A block with a non-finite value has scale NaN and codes 0.
+Q8_BLOCK = 256
+
+
+def q8_code_offset(n: int) -> int:
+    return (4 * (-(-n // Q8_BLOCK)) + 15) // 16 * 16
+
+
+def q8_bytes(n: int) -> int:
+    """Bytes of one encoded segment of ``n`` >= 1 values."""
+    return q8_code_offset(n) + (n + 15) // 16 * 16
+
+
+def q8_encode(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [..., n] -> uint8 [..., q8_bytes(n)] (plain torch; any device)."""
+    n = x.shape[-1]
+    nb = -(-n // Q8_BLOCK)
+    lead = x.shape[:-1]
+    blocks = F.pad(x.float(), (0, nb * Q8_BLOCK - n)).reshape(*lead, nb, Q8_BLOCK)
+    finite = torch.isfinite(blocks).all(-1)
+    amax = torch.where(finite, blocks.abs().amax(-1), torch.zeros_like(blocks[..., 0]))
+    scale = amax * torch.tensor(1.0 / 127.0, dtype=torch.float32, device=x.device)
+    live = (finite & (scale > 0))[..., None]  # not a zero block (or one whose scale underflows to 0)
+    q = torch.where(live, torch.round(blocks / torch.where(live, scale[..., None], torch.ones_like(blocks))),
+                    torch.zeros_like(blocks)).clamp_(-127.0, 127.0)
+    scale = torch.where(finite, scale, torch.full_like(scale, float("nan")))
+    out = torch.zeros(*lead, q8_bytes(n), dtype=torch.uint8, device=x.device)
+    out[..., :4 * nb] = scale.contiguous().view(torch.uint8).reshape(*lead, 4 * nb)
+    co = q8_code_offset(n)
+    out[..., co:co + n] = q.to(torch.int8).reshape(*lead, nb * Q8_BLOCK)[..., :n].contiguous().view(torch.uint8)
+    return out
+
+
+def q8_decode(buf: torch.Tensor, n: int) -> torch.Tensor:
+    """uint8 [..., q8_bytes(n)] -> fp32 [..., n]."""
+    nb = -(-n // Q8_BLOCK)
+    co = q8_code_offset(n)
+    scales = buf[..., :4 * nb].contiguous().view(torch.float32)
+    codes = buf[..., co:co + n].contiguous().view(torch.int8).float()
+    return codes * scales.repeat_interleave(Q8_BLOCK, dim=-1)[..., :n]
+
+
+def _check_q8(buf, rows, n, name):
+    if buf.dtype != torch.uint8 or n < 1 or buf.numel() != rows * q8_bytes(n):
+        raise RuntimeError(f"{name} must be uint8 with {rows} x q8_bytes({n}) = {rows * q8_bytes(max(n, 1))} bytes, "
+                           f"has {buf.numel()} of {buf.dtype}")
+
+
+@_impl("pack_q8")
+def _pack_q8_cpu(src, dst):
+    _check_q8(dst, 1, src.numel(), "dst")
+    dst.copy_(q8_encode(src.reshape(-1)))
+
+
+@_impl("reduce_delta_q8")
+def _reduce_delta_q8_cpu(parts, weights, deltas, n):
+    _check_q8(parts, parts.shape[0], n, "parts")
+    _check_q8(deltas, parts.shape[0], n, "deltas")
+    w = weights.float()
+    tot = float(w.sum())
+    if not tot > 0:  # no weight at all: a no-op round (zero deltas), as the HIP kernel does
+        deltas.zero_()
+        return
+    x = q8_decode(parts, n)
+    avg = x[0] + (w[1:, None] * (x[1:] - x[0])).sum(0) * (1.0 / tot)
+    deltas.copy_(q8_encode(avg[None, :] - x))
+
+
+@_impl("unpack_q8")
+def _unpack_q8_cpu(src, dst, add=False):
+    _check_q8(src, 1, dst.numel(), "src")
+    v = q8_decode(src.reshape(-1), dst.numel())
+    if add:
+        dst.add_(v)
+    else:
+        dst.copy_(v)
 
 
 @_impl("embed_ln_fwd")

@@ -77,7 +77,8 @@ class CollaborativeOptimizer:
                  performance_ema_alpha: float = 0.1, metadata_expiration: float = 30.0,
                  averaging_timeout: Optional[float] = None, step_tolerance: int = 1, client_mode: bool = False,
                  auxiliary: bool = False, allow_state_sharing: bool = True, verbose: bool = False, start: bool = True,
-                 compression_type: str = "FLOAT16", compression: Optional[str] = None, throughput: Optional[float] = None,
+                 compression_type: str = "FLOAT16", compression: Optional[str] = None,
+                 state_averaging_compression: Optional[str] = None, throughput: Optional[float] = None,
                  peer_id: Optional[bytes] = None, max_grad_norm: Optional[float] = None,
                  delay_param_averaging: bool = False, eta_slack: float = 0.0, prejoin: bool = True,
                  **averager_kwargs):
@@ -125,9 +126,14 @@ class CollaborativeOptimizer:
                       "wait_s": 0.0, "fetch_s": 0.0, "averaging_s": 0.0, "matchmaking_s": 0.0, "allreduce_s": 0.0,
                       "optimizer_s": 0.0, "tail_s": 0.0, "local_steps": 0}
 
+        # wire codecs: compression_type for the gradients, state_averaging_compression for the
+        # parameters (default: the same), in the order of the averaged tensors [params, grads]
+        self.grad_compression = compression or compression_type
+        self.state_compression = state_averaging_compression or self.grad_compression
         self.averager = DecentralizedAverager(
             [self.flat.fp32, self.flat.grad], dht, prefix, peer_id=peer_id,
-            compression=compression or compression_type, throughput=throughput, client_mode=client_mode,
+            compression=[self.state_compression, self.grad_compression], throughput=throughput,
+            client_mode=client_mode,
             auxiliary=auxiliary, allow_state_sharing=allow_state_sharing, metadata_expiration=metadata_expiration,
             averaging_timeout=self.averaging_timeout, **averager_kwargs)
         self.averager.get_current_state = self._get_current_state
@@ -413,6 +419,7 @@ class CollaborativeOptimizer:
                                            expected_group_size=cs.num_peers + self._num_aux(),
                                            gather={"step": int(self.local_step)},
                                            tensors=[self.flat.grad] if self.delay_param_averaging else None,
+                                           compression=self.grad_compression if self.delay_param_averaging else None,
                                            prejoined=prejoined)
                 self.stats["averaging_rounds"] += 1
                 if group is None:
@@ -594,10 +601,12 @@ class CollaborativeOptimizer:
             if self.collaboration_state.num_peers >= 1:
                 expected = self.collaboration_state.num_peers + self._num_aux()
                 group = self.averager.step(weight=0.0, timeout=self.averaging_timeout, expected_group_size=expected,
-                                           tensors=[self.flat.grad] if self.delay_param_averaging else None)
+                                           tensors=[self.flat.grad] if self.delay_param_averaging else None,
+                                           compression=self.grad_compression if self.delay_param_averaging else None)
                 if group is not None and self.delay_param_averaging:  # help with the delayed parameter round
                     self.averager.step(weight=0.0, timeout=self.averaging_timeout, expected_group_size=expected,
-                                       tensors=[self.flat.fp32], key_suffix="_params")
+                                       tensors=[self.flat.fp32], key_suffix="_params",
+                                       compression=self.state_compression)
                 if group is not None:
                     steps = [g.get("step") for g in group["gathered"] if isinstance(g.get("step"), int)]
                     current = max([current] + steps)
@@ -667,12 +676,14 @@ class CollaborativeOptimizer:
                         self._side_stream.wait_event(ready)
                         res = self.averager.step(weight=weight, timeout=self.averaging_timeout,
                                                  expected_group_size=expected_group_size, tensors=[self._param_delta],
-                                                 sources=[self._param_snapshot], key_suffix="_params")
+                                                 sources=[self._param_snapshot], key_suffix="_params",
+                                                 compression=self.state_compression)
                         self._param_done_event.record(self._side_stream)
                 else:
                     res = self.averager.step(weight=weight, timeout=self.averaging_timeout,
                                              expected_group_size=expected_group_size, tensors=[self._param_delta],
-                                             sources=[self._param_snapshot], key_suffix="_params")
+                                             sources=[self._param_snapshot], key_suffix="_params",
+                                             compression=self.state_compression)
             except Exception as e:  # noqa: BLE001
                 logger.warning(f"delayed parameter averaging failed: {e}")
                 res = None

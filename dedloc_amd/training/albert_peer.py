@@ -124,7 +124,8 @@ class AlbertPeer:
         self.batch_size_per_step = training_args.per_device_train_batch_size * training_args.gradient_accumulation_steps
         self.collab_opt = CollaborativeOptimizer(
             self.opt, dht=self.dht, scheduler=self.scheduler, prefix=ca.experiment_prefix,
-            compression_type=ca.compression, batch_size_per_step=self.batch_size_per_step,
+            compression_type=ca.compression, state_averaging_compression=ca.state_averaging_compression,
+            batch_size_per_step=self.batch_size_per_step,
             throughput=ca.bandwidth, target_batch_size=ca.target_batch_size - ca.batch_size_lead,
             client_mode=ca.client_mode, verbose=True, start=True, auxiliary=auxiliary,
             allow_state_sharing=not auxiliary, peer_id=self.local_public_key,

@@ -131,6 +131,7 @@ class SwavPeer:
         self.collab_opt = CollaborativeOptimizer(
             self.opt, dht=self.dht, scheduler=self.scheduler, prefix=ocfg.exp_prefix,
             compression_type=str(ocfg.get("compression", "FLOAT16")),
+            state_averaging_compression=ocfg.get("state_averaging_compression", None),
             target_batch_size=int(ocfg.get("target_batch_size", 32768)),
             batch_size_per_step=int(ocfg.batch_size_for_tracking), verbose=True, start=True,
             peer_id=self.local_public_key, target_group_size=int(ocfg.target_group_size),
