@@ -99,15 +99,20 @@ __device__ __forceinline__ int colperm(int c) {
 // every kernel with a K-outer operand (the weight gradients ran ~30% below the K-inner forms).
 // Hidden in asm, the DMAs are ordered only by the pipeline's own counted vmcnt waits; the
 // compiler's waits for its own loads can only get stricter.
-__device__ __forceinline__ void dma16(const bf16_t* src, uint8_t* lds_dst) {
-  const uint32_t m0 = __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(lds_void*)lds_dst);
+// lds_dst is the destination's LDS byte address: lds_addr of the __shared__ array, taken once per
+// kernel, plus the slot offset.  Passed as a generic pointer and cast here, every DMA carried the
+// cast's null check (64-bit scalar add, s_cmp_lg_u64, s_cselect) in front of its s_mov m0: 84 of the
+// K-inner store kernel's 1303 instructions, most of them in the K loop.
+__device__ __forceinline__ uint32_t lds_addr(uint8_t* p) { return (uint32_t)(size_t)(lds_void*)p; }
+__device__ __forceinline__ void dma16(const bf16_t* src, uint32_t lds_dst) {
+  const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds_dst);
   asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, off" ::"s"(m0), "v"(src) : "memory", "m0");
 }
 
 // Issue the two LDS-DMA pieces of this thread for one half-tile.
 template <bool KO, bool ISB>
 __device__ __forceinline__ void stage_half(const bf16_t* __restrict__ g, long ld, int r0, int rows_valid, int k0,
-                                           int half, uint8_t* slot, int w, int lane) {
+                                           int half, uint32_t slot, int w, int lane) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int region = j * 8 + w;  // 1 KiB piece of the 16 KiB image
@@ -150,7 +155,7 @@ __device__ __forceinline__ void src_base(const bf16_t* __restrict__ g, long ld, 
   }
 }
 
-__device__ __forceinline__ void stage_pre(const bf16_t* const (&base)[2], long koff, uint8_t* slot, int w) {
+__device__ __forceinline__ void stage_pre(const bf16_t* const (&base)[2], long koff, uint32_t slot, int w) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) dma16(base[j] + koff, slot + (j * 8 + w) * 1024);
 }
@@ -239,6 +244,7 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(Args p) {
   // EPI_BNBWD: + [4][256] fp32 BatchNorm coefficients of the tile's columns (read per pass from LDS
   // instead of holding 32 registers, which pay for reading the BN input one pass ahead)
   __shared__ __attribute__((aligned(16))) uint8_t smem[SMEM + (EPI == EPI_BNBWD ? 4096 : 0)];
+  const uint32_t lds0 = lds_addr(smem);
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int wm = w >> 2, wn = w & 3;
@@ -279,7 +285,7 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(Args p) {
   // half-tile h = 4 t + k of the stream: k = 0 A0, 1 B1, 2 A1, 3 B0 -> slot k of buffer t & 1
 #define DL_STAGE(T, KSLOT)                                                                          \
   do {                                                                                              \
-    uint8_t* slot_ = smem + ((T) & 1) * BUF + (KSLOT) * HALF;                                       \
+    const uint32_t slot_ = lds0 + ((T) & 1) * BUF + (KSLOT) * HALF;                                 \
     const int k0_ = kbase + (T) * BK;                                                               \
     if constexpr (PRESRC) {                                                                         \
       const long ka_ = AKO ? (long)k0_ * p.lda : (long)k0_, kb_ = BKO ? (long)k0_ * p.ldb : (long)k0_; \
@@ -711,7 +717,10 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(Args p) {
 // DMA source bases computed once with the K-loop tail peeled (weight gradients +5-7%, forward / data
 // gradients +1-3%; the bias+GELU form measured 2% slower with it and keeps the per-K-tile address
 // math) — round 3, profiles/r3_gemm8_keep_b0_*, r3_gemm8_presrc_*.  The losing forms (B0 re-read,
-// persistent deferred-store tiles, 256 x 128 co-resident tiles: profiles/README.md) are gone.
+// persistent deferred-store tiles, 256 x 128 co-resident tiles: profiles/README.md) are gone, and so is
+// a second persistent form that deferred no store but ran the operand prefetch on across the tile
+// seam (grid = CU count, the next tile's first K-tile retired by the last K-tile's counted wait):
+// bit-identical, no scratch, +0.06% on the micro-step (profiles/README.md, "gemm8 tile boundary").
 template <bool AKO, bool BKO, int EPI>
 int launch8(const Args& a, int splits, hipStream_t st) {
   const int tiles = ((a.M + BM - 1) / BM) * (a.N / BN);
