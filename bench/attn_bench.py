@@ -1,6 +1,10 @@
-"""Attention kernel micro-benchmark at ALBERT-large shapes (head_dim 64): forward, backward, TFLOP/s.
+"""Attention kernel micro-benchmark at ALBERT shapes: forward, backward, TFLOP/s.
 
     python bench/attn_bench.py --batch 64 --heads 16 --seq 512 [--pad 0.25]
+    python bench/attn_bench.py --head_dim 128 --impl fused|composed ...
+
+--impl composed runs ops.attn_composed_fwd / _bwd (batched GEMMs + softmax kernel, fp32 scores through
+HBM, no tile skipping) on the same inputs: the path every head size outside ops.FUSED_HEAD_DIMS takes.
 """
 import argparse
 import json
@@ -13,7 +17,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-import dedloc_amd.ops  # noqa: E402,F401
+import dedloc_amd.ops as ops  # noqa: E402
 
 O = torch.ops.dedloc
 
@@ -25,8 +29,11 @@ def main():
     ap.add_argument("--seq", type=int, default=512)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--pad", type=float, default=0.0, help="fraction of each row that is right padding")
+    ap.add_argument("--head_dim", type=int, default=64, choices=(64, 128))
+    ap.add_argument("--impl", choices=("fused", "composed"), default="fused")
     args = ap.parse_args()
-    B, H, S, D = args.batch, args.heads, args.seq, 64
+    B, H, S, D = args.batch, args.heads, args.seq, args.head_dim
+    composed = args.impl == "composed"
     dev = torch.device("cuda")
     qkv = torch.randn(B * S, 3 * H * D, device=dev).bfloat16()
     n = int(round(S * (1 - args.pad)))
@@ -37,21 +44,28 @@ def main():
     scale = 1 / math.sqrt(D)
 
     def fwd():
+        if composed:
+            return ops.attn_composed_fwd(qkv, mbias, H, S, scale)
         return O.attn_fwd(qkv, mbias, H, S, scale, kvinfo)
 
     out, lse = fwd()
     dout = torch.randn_like(out)
 
+    def attn_bwd(db=None):
+        if composed:
+            return ops.attn_composed_bwd(qkv, mbias, out, dout, lse, H, S, scale, db)
+        return O.attn_bwd(qkv, mbias, out, dout, lse, H, S, scale, kvinfo, db)
+
     def bwd():
-        return O.attn_bwd(qkv, mbias, out, dout, lse, H, S, scale, kvinfo)
+        return attn_bwd()
 
     dbias = torch.zeros(3 * H * D, device=dev)
 
     def bwd_fused_bias():  # the model's call: QKV bias gradient inside the backward
-        return O.attn_bwd(qkv, mbias, out, dout, lse, H, S, scale, kvinfo, dbias)
+        return attn_bwd(dbias)
 
     def bwd_then_colsum():  # the previous form: backward, then a column-sum pass over dqkv
-        g = O.attn_bwd(qkv, mbias, out, dout, lse, H, S, scale, kvinfo)
+        g = attn_bwd()
         O.bias_grad(g, dbias, True)
         return g
 
@@ -68,7 +82,7 @@ def main():
         dt = (time.perf_counter() - t) / args.iters
         flops = flop_mult * B * H * S * S * D
         res[name] = {"us": round(dt * 1e6, 1), "tflops": round(flops / dt / 1e12, 1)}
-    print(json.dumps({"B": B, "H": H, "S": S, "D": D, "pad": args.pad, **res}))
+    print(json.dumps({"B": B, "H": H, "S": S, "D": D, "impl": args.impl, "pad": args.pad, **res}))
 
 
 if __name__ == "__main__":

@@ -41,8 +41,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--with_optimizer", action="store_true",
                     help="include clip + LAMB every micro-step (upper bound on optimizer cost)")
+    ap.add_argument("--attn", default="fused", choices=["fused", "composed"],
+                    help="composed: head_dim 128 (albert-xlarge-v2) takes ops.attn_composed_* instead of the flash kernels")
     args = ap.parse_args()
     dev = torch.device("cuda")
+    if args.attn == "composed":
+        import dedloc_amd.ops as ops
+
+        ops.FUSED_HEAD_DIMS = (64,)
     from dedloc_amd.models.albert import AlbertConfig, AlbertForPreTraining, flops_per_sample
 
     cfg = AlbertConfig.from_pretrained(args.config)
@@ -105,7 +111,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
     fl = flops_per_sample(cfg, args.seq, P) * args.batch
-    print(json.dumps({"impl": args.impl, "batch": args.batch, "seq": args.seq, "ms_per_microstep": dt * 1e3,
+    print(json.dumps({"impl": args.impl, "config": args.config, "attn": args.attn, "batch": args.batch, "seq": args.seq, "ms_per_microstep": dt * 1e3,
                       "samples_per_s": args.batch / dt, "tflops": fl / dt / 1e12, "loss": float(loss)}), flush=True)
 
 

@@ -360,10 +360,18 @@ inline const int* kvinfo_ptr(const c10::optional<at::Tensor>& kvinfo, int64_t B)
   return kvinfo->data_ptr<int>();
 }
 
+// the fused kernels exist for these head sizes only (ops.FUSED_HEAD_DIMS); every other size goes
+// through ops.attn_composed_*
+inline void check_head_dim(int64_t D, int64_t ld, int64_t H, const char* what) {
+  TORCH_CHECK((D == 64 || D == 128) && ld == 3 * H * D, "dedloc_amd: ", what, ": head_dim ", D, " (row length ", ld,
+              ", ", H, " heads) is not supported by the fused attention kernels; supported head sizes are 64 and 128");
+}
+
 std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& mbias, int64_t H,
                                             int64_t S, double scale, const c10::optional<at::Tensor>& kvinfo) {
   expect(qkv, at::kBFloat16, "qkv");
   const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H), B = T / S;
+  check_head_dim(D, ld, H, "attn_fwd");
   auto out = at::empty({T, H * D}, qkv.options());
   auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
   const float* mb = nullptr;
@@ -384,6 +392,7 @@ at::Tensor attn_bwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& mbia
   expect(out, at::kBFloat16, "out");
   expect(dout, at::kBFloat16, "dout");
   const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H), B = T / S;
+  check_head_dim(D, ld, H, "attn_bwd");
   auto dqkv = at::empty_like(qkv);
   auto delta = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
   const float* mb = mbias.has_value() ? f32(*mbias) : nullptr;

@@ -183,7 +183,13 @@ int dl_attn_softmax_fwd(const float* s, const float* mbias, bf16_t* p, float* ls
 int dl_attn_softmax_bwd(const float* s, const float* dp, const float* mbias, const float* lse, const float* delta,
                         bf16_t* p, bf16_t* ds, long rows, int H, int S, float c, float scale, hipStream_t st);
 
-// attention.hip
+// attention.hip: head_dim 64 kernels and the entry points, which send D == 128 to
+// attention_hd128.hip (dl_attn_hd128_*: same arguments, same checks, D fixed).  -1 for any other D.
+int dl_attn_hd128_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo,
+                      float* lse, int B, int H, int S, float scale, hipStream_t st);
+int dl_attn_hd128_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, const bf16_t* out,
+                      const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B,
+                      int H, int S, float scale, hipStream_t st);
 int dl_attn_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo, float* lse,
                 int B, int H, int S, int D, float scale, hipStream_t st);
 // dbias (optional, fp32 [3 H D], accumulated): the QKV projection's bias gradient (query: column

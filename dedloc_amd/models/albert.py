@@ -82,9 +82,9 @@ class AlbertConfig:
 
     @classmethod
     def albert_xlarge_v2(cls, **kw) -> "AlbertConfig":
-        """albert-xlarge-v2 (HF model card sizes): 24 x 2048, 16 heads of 128 — outside the fused
-        attention kernels' head_dim 64, so its attention runs the composed path
-        (ops.attn_composed_fwd / _bwd: batched bf16 GEMMs, fp32 scores)."""
+        """albert-xlarge-v2 (HF model card sizes): 24 x 2048, 16 heads of 128 — its attention runs
+        the fused head_dim-128 flash kernels (ops.FUSED_HEAD_DIMS; the composed path,
+        ops.attn_composed_fwd / _bwd, serves head sizes outside that tuple)."""
         base = dict(vocab_size=30000, embedding_size=128, hidden_size=2048, num_hidden_layers=24,
                     num_hidden_groups=1, num_attention_heads=16, intermediate_size=8192, inner_group_num=1)
         base.update(kw)

@@ -130,7 +130,7 @@ def _attn_split(qkv, H, S):
 
 
 def attn_composed_fwd(qkv, mbias, H, S, scale):
-    """Attention for head sizes outside the fused kernels' 64 (albert-xlarge: 128): batched bf16
+    """Attention for head sizes outside ``FUSED_HEAD_DIMS``: batched bf16
     GEMMs with fp32 scores around the ``attn_softmax_fwd`` kernel (scale, key bias, log2-unit
     softmax in one pass) — same inputs / outputs as ``attn_fwd`` (out [B*S, H*D] bf16, lse
     [B, H, S] fp32 in log2 units), but the [B*H, S, S] scores go through HBM."""
@@ -166,12 +166,19 @@ def attn_composed_bwd(qkv, mbias, out, dout, lse, H, S, scale, dbias=None):
     return g
 
 
+# Head sizes the fused flash kernels serve on the GPU; every other size takes the composed path.
+# Benchmarks and tests narrow this tuple (``ops.FUSED_HEAD_DIMS = (64,)``) to run the composed path
+# at head_dim 128.
+FUSED_HEAD_DIMS = (64, 128)
+
+
 def _fused_attention(qkv, H):
-    return not qkv.is_cuda or qkv.shape[-1] // (3 * H) == 64
+    return not qkv.is_cuda or qkv.shape[-1] // (3 * H) in FUSED_HEAD_DIMS
 
 
 def attn_fwd(qkv, mbias, H, S, scale, kvinfo=None):
-    """The fused flash kernels for head_dim 64 (CPU: the fp32 reference), else the composed path."""
+    """The fused flash kernels for the head sizes in ``FUSED_HEAD_DIMS`` (CPU: the fp32 reference),
+    else the composed path."""
     if _fused_attention(qkv, H):
         return OPS.attn_fwd(qkv, mbias, H, S, scale, kvinfo)
     return attn_composed_fwd(qkv, mbias, H, S, scale)
