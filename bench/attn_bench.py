@@ -5,6 +5,11 @@
 
 --impl composed runs ops.attn_composed_fwd / _bwd (batched GEMMs + softmax kernel, fp32 scores through
 HBM, no tile skipping) on the same inputs: the path every head size outside ops.FUSED_HEAD_DIMS takes.
+
+--varlen [--length_mode full|wikitext|uniform] adds the packed variable-length kernels
+(attn_varlen_fwd / _bwd) on rows of those lengths, with TFLOP/s counted on REAL tokens
+(sum len^2), beside the fixed-S figures of the same run ("fwd" / "bwd_fused_bias", full rows) and
+the fixed-S kernels on the same lengths padded to S ("padded_*", kvinfo lengths, real-token FLOPs).
 """
 import argparse
 import json
@@ -31,6 +36,9 @@ def main():
     ap.add_argument("--pad", type=float, default=0.0, help="fraction of each row that is right padding")
     ap.add_argument("--head_dim", type=int, default=64, choices=(64, 128))
     ap.add_argument("--impl", choices=("fused", "composed"), default="fused")
+    ap.add_argument("--varlen", action="store_true", help="also time the packed variable-length kernels")
+    ap.add_argument("--length_mode", choices=("full", "wikitext", "uniform"), default="full")
+    ap.add_argument("--min_len", type=int, default=64)
     args = ap.parse_args()
     B, H, S, D = args.batch, args.heads, args.seq, args.head_dim
     composed = args.impl == "composed"
@@ -69,9 +77,34 @@ def main():
         O.bias_grad(g, dbias, True)
         return g
 
+    cases = [("fwd", fwd, 4, B * S * S), ("bwd", bwd, 10, B * S * S), ("bwd_fused_bias", bwd_fused_bias, 10, B * S * S),
+             ("bwd_then_colsum", bwd_then_colsum, 10, B * S * S)]
+    extra = {}
+    if args.varlen:
+        from dedloc_amd.data.packing import make_seqinfo
+        from dedloc_amd.data.synthetic_mlm import SyntheticSOPStream
+
+        st = SyntheticSOPStream(B, S, 30000, seed=0, length_mode=args.length_mode, min_len=args.min_len)
+        vl = st.next_batch()["attention_mask"].sum(1).tolist()
+        si, si_h, rows, _ = make_seqinfo(vl, dev, tail=False)
+        T = rows[-1]
+        vq = torch.randn(T, 3 * H * D, device=dev).bfloat16()
+        vout, vlse = O.attn_varlen_fwd(vq, si, si_h, H, scale)
+        vdout = torch.randn_like(vout)
+        # the fixed-S kernels on the same lengths, padded to S
+        pkv = torch.cat([torch.tensor(vl, dtype=torch.int32), torch.ones(1, dtype=torch.int32)]).to(dev)
+        pmb = torch.where(torch.arange(S, device=dev)[None] < pkv[:B, None], 0.0, -1e30).float().contiguous()
+        pout, plse = O.attn_fwd(qkv, pmb, H, S, scale, pkv)
+        real = sum(n * n for n in vl)
+        cases += [("varlen_fwd", lambda: O.attn_varlen_fwd(vq, si, si_h, H, scale), 4, real),
+                  ("varlen_bwd_fused_bias", lambda: O.attn_varlen_bwd(vq, si, si_h, vout, vdout, vlse, H, scale, dbias),
+                   10, real),
+                  ("padded_fwd", lambda: O.attn_fwd(qkv, pmb, H, S, scale, pkv), 4, real),
+                  ("padded_bwd_fused_bias", lambda: O.attn_bwd(qkv, pmb, pout, dout, plse, H, S, scale, pkv, dbias),
+                   10, real)]
+        extra = {"length_mode": args.length_mode, "real_token_share": sum(vl) / (B * S), "slot_row_share": T / (B * S)}
     res = {}
-    for name, fn, flop_mult in (("fwd", fwd, 4), ("bwd", bwd, 10), ("bwd_fused_bias", bwd_fused_bias, 10),
-                                ("bwd_then_colsum", bwd_then_colsum, 10)):
+    for name, fn, flop_mult, pairs in cases:
         for _ in range(3):
             fn()
         torch.cuda.synchronize()
@@ -80,9 +113,9 @@ def main():
             fn()
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t) / args.iters
-        flops = flop_mult * B * H * S * S * D
+        flops = flop_mult * H * pairs * D
         res[name] = {"us": round(dt * 1e6, 1), "tflops": round(flops / dt / 1e12, 1)}
-    print(json.dumps({"B": B, "H": H, "S": S, "D": D, "impl": args.impl, "pad": args.pad, **res}))
+    print(json.dumps({"B": B, "H": H, "S": S, "D": D, "impl": args.impl, "pad": args.pad, **extra, **res}))
 
 
 if __name__ == "__main__":

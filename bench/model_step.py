@@ -3,6 +3,11 @@
 --impl dedloc : this framework's kernels (flat buffers, fused ops)
 --impl hf     : HF transformers AlbertForPreTraining, bf16 autocast, PyTorch eager/SDPA —
                 the "PyTorch-eager on MI355X" baseline BASELINE.md asks to record.
+
+--length_mode {full,wikitext,uniform} draws the rows' lengths as SyntheticSOPStream does (a few
+distinct batches, cycled) and --pack_sequences runs them on the packed, padding-free layout
+(data/packing.py) with host-side lengths, as a CPU collator supplies them.  The JSON line reports
+the real-token share sum(len) / (B * S) and the slot-row share T / (B * S') of the timed batches.
 """
 import os as _os
 import sys as _sys
@@ -41,6 +46,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--with_optimizer", action="store_true",
                     help="include clip + LAMB every micro-step (upper bound on optimizer cost)")
+    ap.add_argument("--length_mode", default="full", choices=["full", "wikitext", "uniform"])
+    ap.add_argument("--min_len", type=int, default=64, help="shortest row of --length_mode wikitext / uniform")
+    ap.add_argument("--pack_sequences", action="store_true", help="packed, padding-free batches (dedloc only)")
+    ap.add_argument("--batches", type=int, default=4, help="distinct batches cycled when lengths vary")
+    ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--attn", default="fused", choices=["fused", "composed"],
                     help="composed: head_dim 128 (albert-xlarge-v2) takes ops.attn_composed_* instead of the flash kernels")
     args = ap.parse_args()
@@ -54,13 +64,34 @@ def main():
     cfg = AlbertConfig.from_pretrained(args.config)
     P = round(0.15 * args.seq)
     ids, tt, am, pos, lab, sop, labels = synthetic(args.batch, args.seq, cfg.vocab_size, P, dev)
+    varying = args.length_mode != "full"
+    assert args.impl == "dedloc" or not (varying or args.pack_sequences), "--length_mode / --pack_sequences: dedloc only"
+    data = [(ids, tt, am, pos, lab, sop, [args.seq] * args.batch)]
+    if varying:
+        from dedloc_amd.data.synthetic_mlm import SyntheticSOPStream
+
+        stream = SyntheticSOPStream(args.batch, args.seq, cfg.vocab_size, seed=args.seed, device=dev,
+                                    length_mode=args.length_mode, min_len=args.min_len)
+        data = []
+        for _ in range(args.batches):
+            b = stream.next_batch()
+            lens = stream.last_lengths or b["attention_mask"].sum(1).tolist()  # outside the timed loop
+            data.append((b["input_ids"], b["token_type_ids"], b["attention_mask"], b["mlm_positions"],
+                         b["mlm_labels"], b["sentence_order_label"], lens))
+    Sp = (args.seq + 63) // 64 * 64
+    shares = {"real_token_share": sum(sum(d[6]) for d in data) / (len(data) * args.batch * args.seq),
+              "slot_row_share": sum(sum((n + 63) // 64 * 64 for n in d[6]) for d in data) / (len(data) * args.batch * Sp)}
+    calls = [0]
     if args.impl == "dedloc":
         model = AlbertForPreTraining(cfg)
         model.materialize(dev)
         model.train()
 
         def step():
-            out = model(ids, am, tt, sentence_order_label=sop, mlm_positions=pos, mlm_labels=lab)
+            ids, tt, am, pos, lab, sop, lens = data[calls[0] % len(data)]
+            calls[0] += 1
+            extra = {"pack_sequences": True, "lengths": lens} if args.pack_sequences else {}
+            out = model(ids, am, tt, sentence_order_label=sop, mlm_positions=pos, mlm_labels=lab, **extra)
             out["loss"].backward()
             return out["loss"]
     else:
@@ -104,15 +135,17 @@ def main():
 
     for _ in range(args.warmup):
         step()
+    calls[0] = 0  # the timed loop starts at the first batch, so every arm times the same batches
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.iters):
         loss = step()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
-    fl = flops_per_sample(cfg, args.seq, P) * args.batch
+    fl = flops_per_sample(cfg, args.seq, P) * args.batch  # counted on full rows, whatever the lengths
     print(json.dumps({"impl": args.impl, "config": args.config, "attn": args.attn, "batch": args.batch, "seq": args.seq, "ms_per_microstep": dt * 1e3,
-                      "samples_per_s": args.batch / dt, "tflops": fl / dt / 1e12, "loss": float(loss)}), flush=True)
+                      "samples_per_s": args.batch / dt, "tflops": fl / dt / 1e12, "loss": float(loss.detach()),
+                      "length_mode": args.length_mode, "pack_sequences": bool(args.pack_sequences), **shares}), flush=True)
 
 
 if __name__ == "__main__":

@@ -63,7 +63,7 @@ class DatasetArguments:
                                        metadata={"help": "Path to the model config (the albert-large-v2 URL maps to the built-in config)"})
     cache_dir: Optional[str] = field(default="data", metadata={"help": "Path to the cache"})
     vocab_size: Optional[int] = field(default=None, metadata={"help": "Override the vocabulary size (sahajBERT: 31995)"})
-    length_mode: str = field(default="full", metadata={"help": "synthetic instance lengths: full (all 512) or wikitext (10% short tails)"})
+    length_mode: str = field(default="full", metadata={"help": "synthetic instance lengths: full (all 512), wikitext (10% short tails) or uniform (min_len .. seq_length)"})
     mask_mode: str = field(default="fixed", metadata={"help": "fixed (max_predictions_per_seq form) or hf (Bernoulli 15%)"})
     stream_sources: Optional[str] = field(default=None, metadata={
         "help": "sahajBERT streaming corpus over local text: 'path_a:0.23,path_b:0.77' (tokenized on the fly "
@@ -101,6 +101,7 @@ class AlbertTrainingArguments:
     run_name: Optional[str] = None
     dataloader_num_workers: int = 4
     device: Optional[str] = None
+    pack_sequences: bool = field(default=False, metadata={"help": "run the model on packed, padding-free batches (variable shapes per batch; one device sync per batch when the data stream has no host-side lengths)"})
     # ---- MI355X emulation of the reference's heterogeneous AWS fleet
     throttle: float = field(default=0.0, metadata={"help": "extra idle seconds per training step (emulates a slower peer)"})
     slowdown: float = field(default=1.0, metadata={"help": "emulate slower hardware: each step takes this many times longer"})

@@ -51,6 +51,8 @@ def trainer_argv(a, micro_batch: int) -> List[str]:
         argv += ["--initial_peers", *a.initial_peers]
     if a.device:
         argv += ["--device", a.device]
+    if getattr(a, "pack_sequences", False):
+        argv += ["--pack_sequences", "True"]
     return argv + list(a.extra)
 
 
@@ -62,6 +64,8 @@ def main(argv=None):
     ap.add_argument("--output_dir", default="./outputs")
     ap.add_argument("--device", default=None, help="cuda (default when available) or cpu")
     ap.add_argument("--micro_batch", type=int, default=None, help="override the device-sized micro-batch")
+    ap.add_argument("--pack_sequences", action="store_true",
+                    help="padding-free batches (one long row no longer sets the padding of a small micro-batch)")
     ap.add_argument("--dry_run", action="store_true", help="print the run_trainer arguments and exit")
     ap.add_argument("extra", nargs=argparse.REMAINDER, help="further run_trainer flags after --")
     a = ap.parse_args(argv)

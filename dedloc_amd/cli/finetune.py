@@ -137,14 +137,23 @@ def build_model(task: str, model_path: str, num_labels: int, device) -> torch.nn
     return model
 
 
+def _host_lengths(model, b) -> Dict[str, List[int]]:
+    """--pack_sequences: the rows' lengths, read from the mask while the batch is still on the host
+    (packing then costs no device synchronisation)."""
+    if not getattr(model, "pack_sequences", False):
+        return {}
+    return {"lengths": b["attention_mask"].sum(1).tolist()}
+
+
 @torch.no_grad()
 def evaluate(model, data, task, bs, device) -> Tuple[float, Dict[str, float]]:
     model.eval()
     losses, n = 0.0, 0
     preds, refs = [], []
     for b in batches(data, bs, False, 0):
+        extra = _host_lengths(model, b)
         b = {k: v.to(device) for k, v in b.items()}
-        out = model(b["input_ids"], b["attention_mask"], labels=b["labels"])
+        out = model(b["input_ids"], b["attention_mask"], labels=b["labels"], **extra)
         losses += float(out["loss"]) * b["input_ids"].shape[0]
         n += b["input_ids"].shape[0]
         pred = out["logits"].float().argmax(-1).cpu()
@@ -170,6 +179,7 @@ def run(args) -> Dict[str, float]:
     device = torch.device(args.device or ("cuda" if torch.cuda.is_available() else "cpu"))
     labels = NER_LABELS if args.task == "ner" else NCC_LABELS
     model = build_model(args.task, args.model_path, len(labels), device)
+    model.pack_sequences = bool(getattr(args, "pack_sequences", False))
     V = model.config.vocab_size
     make = synthetic_ner if args.task == "ner" else synthetic_ncc
     train = make(args.train_samples, args.max_seq_length, V, args.seed)
@@ -186,9 +196,10 @@ def run(args) -> Dict[str, float]:
     model.train()
     for epoch in range(args.num_train_epochs):
         for b in batches(train, args.per_device_train_batch_size, True, args.seed + epoch):
+            extra = _host_lengths(model, b)
             b = {k: v.to(device) for k, v in b.items()}
             flat.zero_grad()
-            out = model(b["input_ids"], b["attention_mask"], labels=b["labels"])
+            out = model(b["input_ids"], b["attention_mask"], labels=b["labels"], **extra)
             out["loss"].backward()
             torch.nn.utils.clip_grad_norm_([master], args.max_grad_norm)
             opt.step()
@@ -238,6 +249,8 @@ def parse_args(argv=None):
     ap.add_argument("--eval_samples", type=int, default=128)
     ap.add_argument("--seed", type=int, default=42)
     ap.add_argument("--device", default=None)
+    ap.add_argument("--pack_sequences", action="store_true",
+                    help="run on packed, padding-free batches (head_dim 64 / 128 models; shapes vary per batch)")
     return ap.parse_args(argv)
 
 

@@ -339,6 +339,48 @@ void embed_bwd(const at::Tensor& ds, const at::Tensor& ids, const c10::optional<
         "embed_bwd");
 }
 
+// packed batches: the position of each row is given (int32[T]) instead of derived as row % S
+inline const int* pos_ptr(const at::Tensor& pos, int64_t T) {
+  expect(pos, at::kInt, "pos");
+  TORCH_CHECK(pos.numel() == T, "embed: pos must hold one position per row");
+  TORCH_CHECK(T % 64 == 0, "embed: a packed token buffer is a whole number of 64-row tiles (got ", T, " rows)");
+  return pos.data_ptr<int>();
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> embed_ln_pos_fwd(
+    const at::Tensor& ids, const c10::optional<at::Tensor>& tt, const at::Tensor& pos, const at::Tensor& wemb,
+    const at::Tensor& pemb, const at::Tensor& temb, const at::Tensor& gamma, const at::Tensor& beta, double eps) {
+  expect(ids, at::kLong, "ids");
+  for (auto* t : {&wemb, &pemb, &temb, &gamma, &beta}) expect(*t, at::kFloat, "embedding table");
+  const int64_t T = ids.numel(), E = wemb.size(1);
+  auto opts = wemb.options();
+  auto y = at::empty({T, E}, opts.dtype(at::kBFloat16));
+  auto s = at::empty({T, E}, opts.dtype(at::kBFloat16));
+  auto mean = at::empty({T}, opts);
+  auto rstd = at::empty({T}, opts);
+  const long* ttp = nullptr;
+  if (tt.has_value()) {
+    expect(*tt, at::kLong, "token_type_ids");
+    ttp = tt->data_ptr<long>();
+  }
+  check(dl_embed_ln_pos_fwd(ids.data_ptr<long>(), ttp, pos_ptr(pos, T), f32(wemb), f32(pemb), f32(temb),
+                            f32(gamma), f32(beta), bf(y), bf(s), f32(mean), f32(rstd), (int)T, (int)E, (float)eps,
+                            cur_stream(ids)),
+        "embed_ln_pos_fwd");
+  return {y, s, mean, rstd};
+}
+
+void embed_pos_bwd(const at::Tensor& ds, const at::Tensor& ids, const c10::optional<at::Tensor>& tt,
+                   const at::Tensor& pos, at::Tensor dwemb, at::Tensor dpemb, at::Tensor dtemb) {
+  expect(ds, at::kBFloat16, "ds");
+  for (auto* t : {&dwemb, &dpemb, &dtemb}) expect(*t, at::kFloat, "embedding grad");
+  const int64_t T = ids.numel(), E = ds.size(-1);
+  const long* ttp = tt.has_value() ? tt->data_ptr<long>() : nullptr;
+  check(dl_embed_pos_bwd(cbf(ds), ids.data_ptr<long>(), ttp, pos_ptr(pos, T), f32(dwemb), f32(dpemb),
+                         f32(dtemb), (int)T, (int)E, (int)dtemb.size(0), cur_stream(ds)),
+        "embed_pos_bwd");
+}
+
 std::tuple<at::Tensor, at::Tensor> xent_fwd_bwd(const at::Tensor& logits, const at::Tensor& labels, bool inplace,
                                                 int64_t ignore_index) {
   expect(logits, at::kBFloat16, "logits");
@@ -405,6 +447,78 @@ at::Tensor attn_bwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& mbia
   check(dl_attn_bwd(cbf(qkv), ld, mb, kvinfo_ptr(kvinfo, B), cbf(out), cbf(dout), H * D, f32(lse), f32(delta),
                     bf(dqkv), dbp, (int)B, (int)H, (int)S, (int)D, (float)scale, cur_stream(qkv)),
         "attn_bwd");
+  return dqkv;
+}
+
+// Packed variable-length batches.  seqinfo (device) = int32[2B + 1]: B + 1 row offsets, then B key
+// lengths; seqinfo_host is the same array in host memory — the layout contract is checked on it, so
+// a call costs no device synchronisation, and the largest slot (the grids' x extent) is read from it.
+struct PackedLayout {
+  int64_t B, T, max_slot;
+  const int* dev;
+};
+inline PackedLayout packed_layout(const at::Tensor& seqinfo, const at::Tensor& seqinfo_host, int64_t T,
+                                  const char* what) {
+  expect(seqinfo, at::kInt, "seqinfo");
+  TORCH_CHECK(seqinfo_host.device().is_cpu() && seqinfo_host.scalar_type() == at::kInt && seqinfo_host.is_contiguous(),
+              what, ": seqinfo_host must be a contiguous int32 CPU tensor");
+  const int64_t n = seqinfo_host.numel();
+  TORCH_CHECK(n >= 3 && n % 2 == 1 && seqinfo.numel() == n, what,
+              ": seqinfo must be int32[2B + 1] (B + 1 row offsets, B lengths) on both sides");
+  const int64_t B = (n - 1) / 2;
+  const int* p = seqinfo_host.data_ptr<int>();
+  TORCH_CHECK(p[0] == 0 && p[B] == T, what, ": row offsets must run from 0 to T = ", T, " (got ", p[0], " .. ", p[B],
+              ")");
+  int64_t max_slot = 0;
+  for (int64_t b = 0; b < B; ++b) {
+    const int64_t slot = (int64_t)p[b + 1] - p[b], len = p[B + 1 + b];
+    TORCH_CHECK(p[b] % 64 == 0 && p[b + 1] % 64 == 0, what, ": row offset of sequence ", b,
+                " is not a multiple of 64 (", p[b], ", ", p[b + 1], ")");
+    TORCH_CHECK(slot >= 64, what, ": sequence ", b, " has an empty slot");
+    TORCH_CHECK(len >= 1 && len <= slot, what, ": length ", len, " of sequence ", b, " is outside 1 .. its slot of ",
+                slot, " rows");
+    max_slot = std::max(max_slot, slot);
+  }
+  return PackedLayout{B, T, max_slot, seqinfo.data_ptr<int>()};
+}
+
+std::tuple<at::Tensor, at::Tensor> attn_varlen_fwd(const at::Tensor& qkv, const at::Tensor& seqinfo,
+                                                   const at::Tensor& seqinfo_host, int64_t H, double scale) {
+  expect(qkv, at::kBFloat16, "qkv");
+  const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H);
+  check_head_dim(D, ld, H, "attn_varlen_fwd");
+  const PackedLayout L = packed_layout(seqinfo, seqinfo_host, T, "attn_varlen_fwd");
+  auto out = at::empty({T, H * D}, qkv.options());
+  auto lse = at::empty({H, T}, qkv.options().dtype(at::kFloat));
+  check(dl_attn_varlen_fwd(cbf(qkv), ld, L.dev, bf(out), H * D, f32(lse), (int)L.B, (int)T, (int)L.max_slot, (int)H,
+                           (int)D, (float)scale, cur_stream(qkv)),
+        "attn_varlen_fwd");
+  return {out, lse};
+}
+
+at::Tensor attn_varlen_bwd(const at::Tensor& qkv, const at::Tensor& seqinfo, const at::Tensor& seqinfo_host,
+                           const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse, int64_t H,
+                           double scale, const c10::optional<at::Tensor>& dbias) {
+  expect(qkv, at::kBFloat16, "qkv");
+  expect(out, at::kBFloat16, "out");
+  expect(dout, at::kBFloat16, "dout");
+  expect(lse, at::kFloat, "lse");
+  const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H);
+  check_head_dim(D, ld, H, "attn_varlen_bwd");
+  const PackedLayout L = packed_layout(seqinfo, seqinfo_host, T, "attn_varlen_bwd");
+  TORCH_CHECK(out.numel() == T * H * D && dout.numel() == T * H * D && lse.numel() == H * T,
+              "attn_varlen_bwd: out / dout must be [T, H*D] and lse [H, T]");
+  auto dqkv = at::empty_like(qkv);
+  auto delta = at::empty({H, T}, qkv.options().dtype(at::kFloat));
+  float* dbp = nullptr;
+  if (dbias.has_value()) {
+    expect(*dbias, at::kFloat, "dbias");
+    TORCH_CHECK(dbias->numel() == ld, "dbias must have 3*H*D elements");
+    dbp = f32(*dbias);
+  }
+  check(dl_attn_varlen_bwd(cbf(qkv), ld, L.dev, cbf(out), cbf(dout), H * D, f32(lse), f32(delta), bf(dqkv), dbp,
+                           (int)L.B, (int)T, (int)L.max_slot, (int)H, (int)D, (float)scale, cur_stream(qkv)),
+        "attn_varlen_bwd");
   return dqkv;
 }
 
@@ -1592,6 +1706,10 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("xent_fwd_bwd", &xent_fwd_bwd);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
+  m.impl("attn_varlen_fwd", &attn_varlen_fwd);
+  m.impl("attn_varlen_bwd", &attn_varlen_bwd);
+  m.impl("embed_ln_pos_fwd", &embed_ln_pos_fwd);
+  m.impl("embed_pos_bwd", &embed_pos_bwd);
   m.impl("attn_softmax_fwd", &attn_softmax_fwd);
   m.impl("attn_softmax_bwd", &attn_softmax_bwd);
   m.impl("gemm", &gemm);

@@ -171,6 +171,41 @@ __device__ __forceinline__ int kv_end_of(const int* kvinfo, int B, int b, int S,
   return len;
 }
 
+// Where the rows of one (sequence, head) work item live.  Fixed-S form: sequence b owns rows
+// b*S .. b*S + S of the token buffer, its lse / delta rows start at (b*H + h)*S and the key length
+// comes from kvinfo (above).  Packed form (VARLEN): info = seqinfo = int32[2B + 1], B + 1 row
+// offsets (multiples of 64) followed by B key lengths; sequence b owns the slot
+// rows[b] .. rows[b+1], lse / delta are [H, T] (T arrives in the kernels' S argument) and the
+// length mask always applies, so the generic additive bias is compiled out of the packed kernels.
+// Slots are whole 64-row tiles: no tile load of a work item leaves its slot.
+// (One helper per expression, each used where the fixed-S kernels compute it: their instruction
+// streams are the same with and without the packed instantiations in the file.)
+template <bool VARLEN>
+__device__ __forceinline__ int seq_rows(const int* info, int b, int S) {  // rows of sequence b (its slot)
+  if constexpr (VARLEN) return info[b + 1] - info[b];
+  else return S;
+}
+template <bool VARLEN>
+__device__ __forceinline__ long seq_base(const int* info, int b, int S) {  // its first row in the token buffer
+  if constexpr (VARLEN) return info[b];
+  else return (long)b * S;
+}
+template <bool VARLEN>
+__device__ __forceinline__ int seq_kv_end(const int* info, int B, int b, int S, bool& use_len) {
+  if constexpr (VARLEN) {
+    use_len = true;
+    return info[B + 1 + b];
+  } else {
+    return kv_end_of(info, B, b, S, use_len);
+  }
+}
+// first lse / delta element of (sequence b, head h); T = rows of the packed token buffer
+template <bool VARLEN>
+__device__ __forceinline__ long seq_stat(int b, int h, int H, int S, int T, long rb) {
+  if constexpr (VARLEN) return (long)h * T + rb;
+  else return ((long)b * H + h) * S;
+}
+
 // v_max3_f32 without the canonicalising v_max the compiler inserts in front of fmaxf on MFMA results
 // (MI355X_MICROARCH.md pitfalls): one instruction per two new scores
 __device__ __forceinline__ float vmax3(float a, float b, float c) {

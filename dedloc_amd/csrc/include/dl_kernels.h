@@ -71,6 +71,12 @@ int dl_embed_ln_fwd(const long* ids, const long* tt, const float* wemb, const fl
                     int S, int E, float eps, hipStream_t st);
 int dl_embed_bwd(const bf16_t* ds, const long* ids, const long* tt, float* dwemb, float* dpemb, float* dtemb, int B,
                  int S, int E, int ntypes, hipStream_t st);
+// packed batches: the position of row t is pos[t] (int32[T], the row's offset inside its slot)
+int dl_embed_ln_pos_fwd(const long* ids, const long* tt, const int* pos, const float* wemb, const float* pemb,
+                        const float* temb, const float* gamma, const float* beta, bf16_t* y, bf16_t* s_out, float* mean,
+                        float* rstd, int T, int E, float eps, hipStream_t st);
+int dl_embed_pos_bwd(const bf16_t* ds, const long* ids, const long* tt, const int* pos, float* dwemb, float* dpemb,
+                     float* dtemb, int T, int E, int ntypes, hipStream_t st);
 
 // xent.hip
 int dl_xent_fwd_bwd(const bf16_t* logits, const long* labels, bf16_t* dlogits, float* row_loss, float* loss_out,
@@ -197,6 +203,19 @@ int dl_attn_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinf
 int dl_attn_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, const bf16_t* out,
                 const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int H,
                 int S, int D, float scale, hipStream_t st);
+// Packed variable-length batches: seqinfo = int32[2B + 1] = B + 1 row offsets (multiples of 64,
+// seqinfo[B] == T) then B key lengths (1 <= len <= slot); lse / delta are [H, T]; max_slot is the
+// largest slot (it sizes the grids).  Same kernels as above, compiled with the packed row mapping.
+int dl_attn_hd128_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B,
+                             int T, int max_slot, int H, float scale, hipStream_t st);
+int dl_attn_hd128_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout,
+                             long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T,
+                             int max_slot, int H, float scale, hipStream_t st);
+int dl_attn_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B, int T,
+                       int max_slot, int H, int D, float scale, hipStream_t st);
+int dl_attn_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout, long ldo,
+                       const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T, int max_slot, int H,
+                       int D, float scale, hipStream_t st);
 
 // pool.hip (SwAV trunk pools and head normalisation; channels-last bf16, C % 8 == 0)
 int dl_maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* arg, int N, int H, int W, int C, int P, int Q, hipStream_t st);

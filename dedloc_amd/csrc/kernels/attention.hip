@@ -237,17 +237,23 @@ __device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int
 // Block = NW waves x QS x 32 query rows of one (batch, head).  NW = 8 (ring only): one 512-query
 // block per head at S = 512, so K / V are staged once per head, and each SIMD's two waves belong
 // to one block.
-template <bool RING, int QS, int NW = 4>
+// VARLEN: the packed layout (seq_rows .. seq_stat in dl_attn_tile.h): kvinfo is seqinfo, S_ is T, the grid's x
+// extent covers the largest slot and a block past its own slot leaves before any DMA or barrier.
+template <bool RING, int QS, int NW = 4, bool VARLEN = false>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                           const float* __restrict__ mbias,
                                                           const int* __restrict__ kvinfo, bf16_t* __restrict__ out,
-                                                          long ldo, float* __restrict__ lse, int B, int H, int S,
+                                                          long ldo, float* __restrict__ lse, int B, int H, int S_,
                                                           float sl2, int xcd) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 2 * 64 * 4];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const long rb = (long)b * S;
+  const int S = seq_rows<VARLEN>(kvinfo, b, S_);
+  if constexpr (VARLEN) {
+    if (bid.x * (32 * QS * NW) >= S) return;  // uniform over the block
+  }
+  const long rb = seq_base<VARLEN>(kvinfo, b, S);
   const bf16_t* Qg = qkv + rb * ld + h * HD;
   bool use_len;
   FwdCtx c;
@@ -255,7 +261,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
   c.Vg = qkv + rb * ld + 2L * H * HD + h * HD;
   c.ld = ld;
   c.S = S;
-  c.kv_end = kv_end_of(kvinfo, B, b, S, use_len);
+  c.kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   c.mb_g = (!use_len && mbias) ? mbias + rb : nullptr;
   c.sl2 = sl2;
   c.smem = smem;
@@ -323,7 +329,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
         for (int v = 0; v < 4; ++v)
           store4(op + 32 * t + 8 * v + 4 * hh, o[u][t][4 * v] * inv, o[u][t][4 * v + 1] * inv,
                  o[u][t][4 * v + 2] * inv, o[u][t][4 * v + 3] * inv);
-      if (hh == 0) lse[((long)b * H + h) * S + q[u]] = m[u] + log2f(l[u]);
+      if (hh == 0) lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q[u]] = m[u] + log2f(l[u]);
     }
   }
 }
@@ -332,26 +338,30 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
 // Also computes delta = rowsum(dO * O) for its queries and publishes it for the dkdv kernel.
 // QS = 32-row query sub-blocks per wave (as in the forward: every K / V fragment read from LDS
 // feeds QS MFMAs, and each wave carries QS independent chains).
-template <bool RING, int QS>
+template <bool RING, int QS, bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                              const float* __restrict__ mbias,
                                                              const int* __restrict__ kvinfo,
                                                              const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout,
                                                              long ldo, const float* __restrict__ lse,
                                                              float* __restrict__ delta, bf16_t* __restrict__ dqkv,
-                                                             float* __restrict__ dbias, int B, int H, int S, float sl2,
+                                                             float* __restrict__ dbias, int B, int H, int S_, float sl2,
                                                              float scale, int xcd) {
   // tail: mask bias / bias-grad partials (the epilogue reuses the first 33 KiB for its column sums)
   __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 4 * 64 * 4];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const long rb = (long)b * S;
+  const int S = seq_rows<VARLEN>(kvinfo, b, S_);
+  if constexpr (VARLEN) {
+    if (bid.x * (128 * QS) >= S) return;  // uniform over the block
+  }
+  const long rb = seq_base<VARLEN>(kvinfo, b, S);
   const bf16_t* Qg = qkv + rb * ld + h * HD;
   const bf16_t* Kg = qkv + rb * ld + (long)H * HD + h * HD;
   const bf16_t* Vg = qkv + rb * ld + 2L * H * HD + h * HD;
   bool use_len;
-  const int kv_end = kv_end_of(kvinfo, B, b, S, use_len);
+  const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   const float* mb_g = (!use_len && mbias) ? mbias + rb : nullptr;
   float* mbs = reinterpret_cast<float*>(smem + 4 * TILE_BYTES);
   const int nt = (kv_end + 63) / 64;
@@ -383,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
       for (int e = 0; e < 8; ++e) dl[u] += (float)df[u][ks][e] * (float)of[e];
     }
     dl[u] += __shfl_xor(dl[u], 32, 64);
-    l2[u] = lse[((long)b * H + h) * S + qc];
+    l2[u] = lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + qc];
     if constexpr (RING) {
       settle(l2[u]);
       settle(dl[u]);
@@ -500,7 +510,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
   if constexpr (RING) __syncthreads();  // every wave is done with the ring before the epilogue reuses it
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
-    if (q[u] < S && hh == 0) delta[((long)b * H + h) * S + q[u]] = dl[u];
+    if (q[u] < S && hh == 0) delta[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q[u]] = dl[u];
     if (q[u] < S) {
       bf16_t* dp_ = dqkv + (rb + q[u]) * ld + h * HD;
 #pragma unroll
@@ -577,29 +587,33 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
 // KS = 32-key sub-blocks per wave: with KS = 2 every Q / dO fragment read from LDS feeds two
 // MFMAs; the dK/dV accumulators (128 registers) need the whole 512-entry register file, so that
 // form runs one wave per SIMD (launch bound 256 x 1) and hides latency by ILP instead of waves.
-template <bool RING, int KS>
+template <bool RING, int KS, bool VARLEN = false>
 __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ qkv, long ld, const float* __restrict__ mbias, const int* __restrict__ kvinfo,
     const bf16_t* __restrict__ dout, long ldo, const float* __restrict__ lse, const float* __restrict__ delta,
-    bf16_t* __restrict__ dqkv, int B, int H, int S, float sl2, float scale, int xcd) {
+    bf16_t* __restrict__ dqkv, int B, int H, int S_, float sl2, float scale, int xcd) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 2 * 2 * 64 * 4];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const long rb = (long)b * S;
+  const int S = seq_rows<VARLEN>(kvinfo, b, S_);
+  if constexpr (VARLEN) {
+    if (bid.x * (128 * KS) >= S) return;  // uniform over the block
+  }
+  const long rb = seq_base<VARLEN>(kvinfo, b, S);
   const bf16_t* Qg = qkv + rb * ld + h * HD;
   const bf16_t* Kg = qkv + rb * ld + (long)H * HD + h * HD;
   const bf16_t* Vg = qkv + rb * ld + 2L * H * HD + h * HD;
   const bf16_t* dOg = dout + rb * ldo + h * HD;
-  const float* lse_g = lse + ((long)b * H + h) * S;
-  const float* del_g = delta + ((long)b * H + h) * S;
+  const float* lse_g = lse + seq_stat<VARLEN>(b, h, H, S, S_, rb);
+  const float* del_g = delta + seq_stat<VARLEN>(b, h, H, S, S_, rb);
   float* rowv = reinterpret_cast<float*>(smem + 4 * TILE_BYTES);  // [2 buf][lse 64 | delta 64]
 
   int k[KS];
 #pragma unroll
   for (int u = 0; u < KS; ++u) k[u] = bid.x * (128 * KS) + w * (32 * KS) + 32 * u + r;
   bool use_len;
-  const int kv_end = kv_end_of(kvinfo, B, b, S, use_len);
+  const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   if (use_len && bid.x * (128 * KS) >= kv_end) {  // every key of this block is padding: dK = dV = 0
 #pragma unroll
     for (int u = 0; u < KS; ++u) {
@@ -817,5 +831,38 @@ int dl_attn_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinf
   dim3 grid_kv((S + 127) / 128, H, B);
   attn_bwd_dkdv_kernel<false, 1><<<grid_kv, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H,
                                                           S, sl2, scale, kAttnXcd);
+  return 0;
+}
+
+// Packed (variable-length) batches: seqinfo = int32[2B + 1] (row offsets, then key lengths), lse /
+// delta [H, T]; max_slot (the largest slot, host side) sizes the grids.  The callers validate the
+// layout contract (csrc/bindings.cpp).
+int dl_attn_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B, int T,
+                       int max_slot, int H, int D, float scale, hipStream_t st) {
+  if (!seqinfo || B < 1 || T % 64 != 0 || max_slot < 64 || max_slot % 64 != 0 || max_slot > T) return -1;
+  if (D == 128) return dl_attn_hd128_varlen_fwd(qkv, ld, seqinfo, out, ldo, lse, B, T, max_slot, H, scale, st);
+  if (D != HD || ld % 8 != 0 || ldo % 8 != 0) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  dim3 grid((max_slot + 255) / 256, H, B);
+  attn_fwd_kernel<true, 2, 4, true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, ldo, lse, B, H, T, sl2,
+                                                          kAttnXcd);
+  return 0;
+}
+
+int dl_attn_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout, long ldo,
+                       const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T, int max_slot, int H,
+                       int D, float scale, hipStream_t st) {
+  if (!seqinfo || B < 1 || T % 64 != 0 || max_slot < 64 || max_slot % 64 != 0 || max_slot > T) return -1;
+  if (D == 128)
+    return dl_attn_hd128_varlen_bwd(qkv, ld, seqinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, T, max_slot, H, scale,
+                                    st);
+  if (D != HD || ld % 8 != 0 || ldo % 8 != 0) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  dim3 grid_dq((max_slot + 255) / 256, H, B);
+  attn_bwd_dq_kernel<true, 2, true><<<grid_dq, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, dout, ldo, lse, delta,
+                                                             dqkv, dbias, B, H, T, sl2, scale, kAttnXcd);
+  dim3 grid_kv((max_slot + 127) / 128, H, B);
+  attn_bwd_dkdv_kernel<false, 1, true><<<grid_kv, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv,
+                                                                B, H, T, sl2, scale, kAttnXcd);
   return 0;
 }

@@ -151,23 +151,30 @@ __device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int
   }
 }
 
+// VARLEN: the packed layout (seq_rows .. seq_stat in dl_attn_tile.h): kvinfo is seqinfo, S_ is T, the grid's x
+// extent covers the largest slot and a block past its own slot leaves before any DMA or barrier.
+template <bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn128_fwd_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                              const float* __restrict__ mbias,
                                                              const int* __restrict__ kvinfo, bf16_t* __restrict__ out,
-                                                             long ldo, float* __restrict__ lse, int B, int H, int S,
+                                                             long ldo, float* __restrict__ lse, int B, int H, int S_,
                                                              float sl2, int xcd) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * STAGE];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const long rb = (long)b * S;
+  const int S = seq_rows<VARLEN>(kvinfo, b, S_);
+  if constexpr (VARLEN) {
+    if (bid.x * QB >= S) return;  // uniform over the block
+  }
+  const long rb = seq_base<VARLEN>(kvinfo, b, S);
   const bf16_t* Qg = qkv + rb * ld + h * HD;
   bool use_len;
   FwdCtx c;
   c.Kg = qkv + rb * ld + (long)H * HD + h * HD;
   c.Vg = qkv + rb * ld + 2L * H * HD + h * HD;
   c.ld = ld;
-  c.kv_end = kv_end_of(kvinfo, B, b, S, use_len);
+  c.kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   c.mb_g = (!use_len && mbias) ? mbias + rb : nullptr;
   c.sl2 = sl2;
   c.smem = smem;
@@ -207,28 +214,33 @@ __global__ __launch_bounds__(256, 2) void attn128_fwd_kernel(const bf16_t* __res
       for (int v = 0; v < 4; ++v)
         store4(op + 32 * t + 8 * v + 4 * hh, o[t][4 * v] * inv, o[t][4 * v + 1] * inv, o[t][4 * v + 2] * inv,
                o[t][4 * v + 3] * inv);
-    if (hh == 0) lse[((long)b * H + h) * S + q] = m + log2f(l);
+    if (hh == 0) lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q] = m + log2f(l);
   }
 }
 
 // ------------------------------------------------------------------------------------------ bwd dq
 // Also computes delta = rowsum(dO * O) for its queries and publishes it for the dkdv kernel.
+template <bool VARLEN = false>
 __global__ __launch_bounds__(256, 2) void attn128_bwd_dq_kernel(
     const bf16_t* __restrict__ qkv, long ld, const float* __restrict__ mbias, const int* __restrict__ kvinfo,
     const bf16_t* __restrict__ out, const bf16_t* __restrict__ dout, long ldo, const float* __restrict__ lse,
-    float* __restrict__ delta, bf16_t* __restrict__ dqkv, float* __restrict__ dbias, int B, int H, int S, float sl2,
+    float* __restrict__ delta, bf16_t* __restrict__ dqkv, float* __restrict__ dbias, int B, int H, int S_, float sl2,
     float scale, int xcd) {
   // the epilogue reuses the first 33 KiB for its column sums
   __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * STAGE];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const long rb = (long)b * S;
+  const int S = seq_rows<VARLEN>(kvinfo, b, S_);
+  if constexpr (VARLEN) {
+    if (bid.x * QB >= S) return;  // uniform over the block
+  }
+  const long rb = seq_base<VARLEN>(kvinfo, b, S);
   const bf16_t* Qg = qkv + rb * ld + h * HD;
   const bf16_t* Kg = qkv + rb * ld + (long)H * HD + h * HD;
   const bf16_t* Vg = qkv + rb * ld + 2L * H * HD + h * HD;
   bool use_len;
-  const int kv_end = kv_end_of(kvinfo, B, b, S, use_len);
+  const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   const float* mb_g = (!use_len && mbias) ? mbias + rb : nullptr;
   const int nt = (kv_end + 63) / 64;
   auto issue = [&](int st) {  // key tile st -> slot st % NBUF
@@ -253,7 +265,7 @@ __global__ __launch_bounds__(256, 2) void attn128_bwd_dq_kernel(
     for (int e = 0; e < 8; ++e) dl += (float)df[ks][e] * (float)of[e];
   }
   dl += __shfl_xor(dl, 32, 64);
-  float l2 = lse[((long)b * H + h) * S + qc];
+  float l2 = lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + qc];
   settle(l2);
   settle(dl);
 #pragma unroll
@@ -313,7 +325,7 @@ __global__ __launch_bounds__(256, 2) void attn128_bwd_dq_kernel(
     }
   }
   __syncthreads();  // every wave is done with the ring before the epilogue reuses it
-  if (q < S && hh == 0) delta[((long)b * H + h) * S + q] = dl;
+  if (q < S && hh == 0) delta[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q] = dl;
   if (q < S) {
     bf16_t* dp_ = dqkv + (rb + q) * ld + h * HD;
 #pragma unroll
@@ -384,26 +396,30 @@ __global__ __launch_bounds__(256, 2) void attn128_bwd_dq_kernel(
 // ------------------------------------------------------------------------------------------ bwd dkdv
 // One 32-key sub-block per wave; Q / dO blocks (and lse / delta) of 64 queries stream through the ring.
 // NB = ring slots: with one workgroup per CU the LDS has room for a deeper ring than the forward's.
-template <int NB>
+template <int NB, bool VARLEN = false>
 __global__ __launch_bounds__(256, 1) void attn128_bwd_dkdv_kernel(
     const bf16_t* __restrict__ qkv, long ld, const float* __restrict__ mbias, const int* __restrict__ kvinfo,
     const bf16_t* __restrict__ dout, long ldo, const float* __restrict__ lse, const float* __restrict__ delta,
-    bf16_t* __restrict__ dqkv, int B, int H, int S, float sl2, float scale, int xcd) {
+    bf16_t* __restrict__ dqkv, int B, int H, int S_, float sl2, float scale, int xcd) {
   __shared__ __attribute__((aligned(16))) uint8_t smem[NB * STAGE];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const long rb = (long)b * S;
+  const int S = seq_rows<VARLEN>(kvinfo, b, S_);
+  if constexpr (VARLEN) {
+    if (bid.x * QB >= S) return;  // uniform over the block
+  }
+  const long rb = seq_base<VARLEN>(kvinfo, b, S);
   const bf16_t* Qg = qkv + rb * ld + h * HD;
   const bf16_t* Kg = qkv + rb * ld + (long)H * HD + h * HD;
   const bf16_t* Vg = qkv + rb * ld + 2L * H * HD + h * HD;
   const bf16_t* dOg = dout + rb * ldo + h * HD;
-  const float* lse_g = lse + ((long)b * H + h) * S;
-  const float* del_g = delta + ((long)b * H + h) * S;
+  const float* lse_g = lse + seq_stat<VARLEN>(b, h, H, S, S_, rb);
+  const float* del_g = delta + seq_stat<VARLEN>(b, h, H, S, S_, rb);
 
   const int k = bid.x * QB + w * 32 + r;
   bool use_len;
-  const int kv_end = kv_end_of(kvinfo, B, b, S, use_len);
+  const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   if (use_len && bid.x * QB >= kv_end) {  // every key of this block is padding: dK = dV = 0
     if (k < S) {
       bf16_t* dkp = dqkv + (rb + k) * ld + (long)H * HD + h * HD;
@@ -527,7 +543,7 @@ int dl_attn_hd128_fwd(const bf16_t* qkv, long ld, const float* mbias, const int*
   if (S % 64 != 0 || ld % 8 != 0 || ldo % 8 != 0) return -1;
   const float sl2 = scale * 1.4426950408889634f;
   dim3 grid((S + QB - 1) / QB, H, B);
-  attn128_fwd_kernel<<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, sl2, kAttnXcd);
+  attn128_fwd_kernel<false><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, sl2, kAttnXcd);
   return 0;
 }
 
@@ -537,9 +553,32 @@ int dl_attn_hd128_bwd(const bf16_t* qkv, long ld, const float* mbias, const int*
   if (S % 64 != 0 || ld % 8 != 0 || ldo % 8 != 0) return -1;
   const float sl2 = scale * 1.4426950408889634f;
   dim3 grid((S + QB - 1) / QB, H, B);  // query blocks for dQ, key blocks for dK/dV: both 128 rows
-  attn128_bwd_dq_kernel<<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, H, S,
+  attn128_bwd_dq_kernel<false><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, H, S,
                                               sl2, scale, kAttnXcd);
   attn128_bwd_dkdv_kernel<KV_NBUF><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H, S, sl2,
                                                 scale, kAttnXcd);
+  return 0;
+}
+
+// Packed (variable-length) batches (dl_attn_varlen_fwd / _bwd in attention.hip check the layout arguments)
+int dl_attn_hd128_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B,
+                             int T, int max_slot, int H, float scale, hipStream_t st) {
+  if (ld % 8 != 0 || ldo % 8 != 0) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  dim3 grid((max_slot + QB - 1) / QB, H, B);
+  attn128_fwd_kernel<true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, ldo, lse, B, H, T, sl2, kAttnXcd);
+  return 0;
+}
+
+int dl_attn_hd128_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout,
+                             long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T,
+                             int max_slot, int H, float scale, hipStream_t st) {
+  if (ld % 8 != 0 || ldo % 8 != 0) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  dim3 grid((max_slot + QB - 1) / QB, H, B);
+  attn128_bwd_dq_kernel<true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, dout, ldo, lse, delta, dqkv, dbias,
+                                                    B, H, T, sl2, scale, kAttnXcd);
+  attn128_bwd_dkdv_kernel<KV_NBUF, true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv,
+                                                               B, H, T, sl2, scale, kAttnXcd);
   return 0;
 }

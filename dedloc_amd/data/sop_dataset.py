@@ -136,6 +136,7 @@ class DiskSOPStream:
         self.gen = torch.Generator().manual_seed(int(seed) % (2 ** 63))
         self.order: List[int] = []
         self.epoch = 0
+        self.last_lengths: Optional[List[int]] = None  # host lengths of the last batch (data/packing.py)
 
     def _next_indices(self) -> List[int]:
         out = []
@@ -148,7 +149,9 @@ class DiskSOPStream:
 
     @torch.no_grad()
     def next_batch(self) -> Dict[str, torch.Tensor]:
-        return collate_mlm(self.ds[self._next_indices()], self.meta, self.gen, self.p, self.device)
+        rows = self.ds[self._next_indices()]
+        self.last_lengths = [len(r) for r in rows["input_ids"]]
+        return collate_mlm(rows, self.meta, self.gen, self.p, self.device)
 
 
 @torch.no_grad()
@@ -232,6 +235,7 @@ class StreamingSOPStream:
         self.shuffle_buffer = max(1, shuffle_buffer)
         self.pending: List[Dict[str, List[int]]] = []
         self.source_counts = [0] * len(self.paths)
+        self.last_lengths: Optional[List[int]] = None  # host lengths of the last batch (data/packing.py)
 
     @staticmethod
     def _cycle(path):
@@ -258,6 +262,7 @@ class StreamingSOPStream:
             self.pending.extend(self.builder.from_document(self._draw_document()))
         rows, self.pending = self.pending[:self.B], self.pending[self.B:]
         cols = {k: [r[k] for r in rows] for k in rows[0]}
+        self.last_lengths = [len(r) for r in cols["input_ids"]]
         return collate_mlm(cols, self.meta, self.gen, self.p, self.device)
 
 

@@ -7,7 +7,9 @@ The reference tokenizes WikiText-103 into sentence-order-prediction instances
 non-special tokens (80 % [MASK], 10 % random, 10 % unchanged).  There is no network here, so the
 same columns are generated on the device from a per-peer seed (the reference seeds shuffling with
 ``hash(local_public_key)``, run_trainer.py:266-270): random token ids, full 512-token instances
-by default (``length_mode="wikitext"`` adds the short document-tail instances).
+by default (``length_mode="wikitext"`` adds the short document-tail instances;
+``length_mode="uniform"`` draws every length uniformly from ``[min_len, S]`` — for tests and
+measurements of the padding-free path, data/packing.py).
 
 Two masking forms:
   * ``fixed`` — exactly round(0.15 * n_real) positions per sequence, returned as fixed-shape
@@ -39,8 +41,14 @@ class SyntheticSOPStream:
         # FIRST_REGULAR_ID + (phase + i) % pattern_period with a random phase per row, so a masked
         # token is predictable from its neighbours; 0: independent uniform tokens (throughput runs)
         self.pattern_period = int(pattern_period)
+        if length_mode not in ("full", "wikitext", "uniform"):
+            raise ValueError(f"unknown length_mode {length_mode!r}")
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(int(seed) % (2 ** 63))
+        # "uniform" draws its lengths on the host (its own generator), so they are known there and
+        # packing needs no device synchronisation; the other modes' random streams are untouched
+        self.len_gen = torch.Generator().manual_seed(int(seed) % (2 ** 63))
+        self.last_lengths = None  # host lengths of the last batch, where the host knows them
         self.P = max(1, round(self.p * (seq_len - 3)))
         sd = (seq_len * self.p * (1 - self.p)) ** 0.5
         self.P_hf = min(seq_len, int(-(-(self.p * seq_len + 6 * sd) // 8) * 8))
@@ -57,8 +65,15 @@ class SyntheticSOPStream:
     @torch.no_grad()
     def next_batch(self) -> Dict[str, torch.Tensor]:
         B, S, dev = self.B, self.S, self.device
+        self.last_lengths = None
         if self.length_mode == "full":
             lengths = torch.full((B,), S, device=dev)
+            self.last_lengths = [S] * B
+        elif self.length_mode == "uniform":
+            lo = max(8, min(self.min_len, S))  # never below 8 tokens ([CLS] A [SEP] B [SEP] needs 5)
+            host = torch.randint(lo, S + 1, (B,), generator=self.len_gen)
+            self.last_lengths = host.tolist()
+            lengths = host.to(dev)
         else:  # ~10 % short document tails (the last instance of each document)
             lo = min(self.min_len, max(8, S // 2))  # short sequences: never below 8 tokens
             short = torch.rand(B, generator=self.gen, device=dev) < 0.1

@@ -26,6 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from ..data.packing import PackedBatch, pack_batch, unpack_rows
 from ..utils.flat import FlatParams
 
 NEG_BIG = -1.0e30
@@ -166,9 +167,12 @@ class _AlbertLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, mask, lv, H, S, eps):
         O = ops.OPS
-        mbias, kvinfo = mask
         qkv = O.gemm(h, lv["wqkv"], lv["bqkv32"], None, False, True, 0)
-        att, lse = ops.attn_fwd(qkv, mbias, H, S, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)), kvinfo)
+        if isinstance(mask, PackedBatch):  # packed variable-length batch: h is [T, hidden], S is unused
+            att, lse = ops.attn_varlen_fwd(qkv, mask, H, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)))
+        else:
+            mbias, kvinfo = mask
+            att, lse = ops.attn_fwd(qkv, mbias, H, S, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)), kvinfo)
         if _RESIDUAL_IN_GEMM:
             # residual sums ride in the GEMM epilogues (C = h, beta = 1): the LayerNorms then read one
             # tensor and write one (s is the GEMM output itself) — 2 of 4 LN HBM passes removed
@@ -211,8 +215,12 @@ class _AlbertLayerFn(torch.autograd.Function):
         datt = _dgrad(O, ds1, lv, "wo", None)
         # the QKV bias gradient rides in the attention backward (query: colsum dQ, value: colsum
         # datt, key: exactly zero — softmax is shift invariant), no separate column-sum pass
-        dqkv = ops.attn_bwd(qkv, ctx.mask[0], att, datt, lse, H, ctx.S, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)),
-                          ctx.mask[1], lv["gbqkv"])
+        if isinstance(ctx.mask, PackedBatch):
+            dqkv = ops.attn_varlen_bwd(qkv, ctx.mask, att, datt, lse, H, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)),
+                                       lv["gbqkv"])
+        else:
+            dqkv = ops.attn_bwd(qkv, ctx.mask[0], att, datt, lse, H, ctx.S, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)),
+                                ctx.mask[1], lv["gbqkv"])
         _wgrad(O, dqkv, h, lv, "gwqkv")
         dh = _dgrad(O, dqkv, lv, "wqkv", ds1)
         return dh, None, None, None, None, None
@@ -250,6 +258,9 @@ class AlbertPreTrainedModel(nn.Module):
     added by the subclasses (pre-training, sequence / token classification)."""
 
     add_pooler = True
+    # Run forward on a packed, padding-free token buffer (data/packing.py): set by the trainers'
+    # --pack_sequences, or per call with forward(..., pack_sequences=True).  Off by default.
+    pack_sequences = False
 
     def __init__(self, config: AlbertConfig):
         super().__init__()
@@ -411,10 +422,22 @@ class AlbertPreTrainedModel(nn.Module):
         c = self.config
         return _AlbertLayerFn.apply(h, mask, lv, c.num_attention_heads, S, c.layer_norm_eps)
 
-    def encode(self, input_ids, attention_mask=None, token_type_ids=None):
-        """Returns (sequence_output [B*S', H] bf16, S') where S' is S padded to a multiple of 64."""
+    def _packed(self, pack_sequences, input_ids, attention_mask, token_type_ids, lengths, labels=None):
+        """The PackedBatch of this call, or None when the call runs on the rectangular layout."""
+        if not (self.pack_sequences if pack_sequences is None else pack_sequences):
+            return None
+        batch = {"input_ids": input_ids, "attention_mask": attention_mask, "token_type_ids": token_type_ids}
+        if labels is not None:
+            batch["labels"] = labels
+        return pack_batch(batch, lengths, self.config.pad_token_id)
+
+    def encode(self, input_ids=None, attention_mask=None, token_type_ids=None, packed: Optional[PackedBatch] = None):
+        """Returns (sequence_output [B*S', H] bf16, S') where S' is S padded to a multiple of 64; with
+        ``packed`` the trunk runs on the packed token buffer and returns ([T, H] bf16, None)."""
         assert self.flat is not None, "call model.materialize(device) first"
         c, f = self.config, self.flat
+        if packed is not None:
+            return self._encode_packed(packed), None
         B, S = input_ids.shape
         Sp = (S + 63) // 64 * 64
         if attention_mask is None:
@@ -442,6 +465,30 @@ class AlbertPreTrainedModel(nn.Module):
                    f.g(emb + "token_type_embeddings.weight"), f.g(emb + "LayerNorm.weight"),
                    f.g(emb + "LayerNorm.bias")),
             eps=c.layer_norm_eps)
+        return self._layers(x, mask, Sp), Sp
+
+    def _encode_packed(self, packed: PackedBatch):
+        c, f = self.config, self.flat
+        assert packed.max_slot <= c.max_position_embeddings, "sequence longer than max_position_embeddings"
+        D = c.hidden_size // c.num_attention_heads
+        if D not in ops.FUSED_HEAD_DIMS:
+            raise RuntimeError(f"dedloc_amd: pack_sequences needs a fused attention head size {ops.FUSED_HEAD_DIMS}, "
+                               f"this model has head_dim {D}")
+        emb = "albert.embeddings."
+        x = ops.embed_layernorm_packed(
+            packed.input_ids, packed.token_type_ids, packed.positions, f.p(emb + "word_embeddings.weight"),
+            f.p(emb + "position_embeddings.weight"), f.p(emb + "token_type_embeddings.weight"),
+            f.p(emb + "LayerNorm.weight"), f.p(emb + "LayerNorm.bias"),
+            grads=(f.g(emb + "word_embeddings.weight"), f.g(emb + "position_embeddings.weight"),
+                   f.g(emb + "token_type_embeddings.weight"), f.g(emb + "LayerNorm.weight"),
+                   f.g(emb + "LayerNorm.bias")),
+            eps=c.layer_norm_eps)
+        return self._layers(x, packed, 0)
+
+    def _layers(self, x, mask, Sp):
+        """Mapping-in GEMM and the shared layer group(s) over a [rows, E] embedding output; ``mask`` is
+        the rectangular (mbias, kvinfo) pair or a PackedBatch."""
+        c, f = self.config, self.flat
         m = "albert.encoder.embedding_hidden_mapping_in."
         h = ops.linear(x, f.w(m + "weight"), f.w(m + "bias"), f.g(m + "weight"), f.g(m + "bias"))
         views = [[self._layer_views(g, i) for i in range(c.inner_group_num)] for g in range(c.num_hidden_groups)]
@@ -459,7 +506,7 @@ class AlbertPreTrainedModel(nn.Module):
                     # write the weight's gradient slabs, the first application sums them in
                     lv = dict(lv, wg_first=layer == uses[-1], wg_last=layer == uses[0])
                 h = self._albert_layer(h, lv, mask, Sp)
-        return h, Sp
+        return h
 
     def num_parameters(self) -> int:
         return sum(p.numel() for p in self._p.values())
@@ -488,27 +535,43 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         return sd
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, sentence_order_label=None,
-                mlm_positions=None, mlm_labels=None, return_logits=False):
+                mlm_positions=None, mlm_labels=None, return_logits=False, pack_sequences=None, lengths=None):
         """HF-compatible pre-training forward.
 
         MLM targets either as HF ``labels`` [B, S] (-100 = ignore) or as fixed-shape
         ``mlm_positions``/``mlm_labels`` [B, P] (BERT's max_predictions_per_seq form; -100 pads) —
         the fixed form needs no host synchronisation and is graph-capturable.
+
+        ``pack_sequences`` (default: the model's attribute) runs the same computation on the packed,
+        padding-free token buffer; ``lengths`` are the rows' host-side lengths (without them one
+        device synchronisation reads them from ``attention_mask``).  Inputs and ``out`` are unchanged.
         """
         c, f = self.config, self.flat
         B, S = input_ids.shape
-        h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
+        pk = self._packed(pack_sequences, input_ids, attention_mask, token_type_ids, lengths,
+                          labels if mlm_positions is None else None)
+        if pk is not None:
+            h, _ = self.encode(packed=pk)
+            row0 = pk.row_start  # first row of each sequence: (b, position) -> row0[b] + position
+        else:
+            h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
+            row0 = torch.arange(B, device=h.device) * Sp
         out = {}
         # ---- MLM head on masked positions only
         if mlm_positions is None and labels is not None:
-            flat_lab = labels.reshape(-1)
-            pos = torch.nonzero(flat_lab != -100).squeeze(1)
-            b_idx, s_idx = pos // S, pos % S
-            rows = b_idx * Sp + s_idx
-            tgt = flat_lab[pos]
+            if pk is not None:  # packed labels keep the (b, position) order of the rectangular ones
+                flat_lab = pk.extras["labels"]
+                rows = torch.nonzero(flat_lab != -100).squeeze(1)
+                tgt = flat_lab[rows]
+            else:
+                flat_lab = labels.reshape(-1)
+                pos = torch.nonzero(flat_lab != -100).squeeze(1)
+                b_idx, s_idx = pos // S, pos % S
+                rows = b_idx * Sp + s_idx
+                tgt = flat_lab[pos]
         elif mlm_positions is not None:
             P = mlm_positions.shape[1]
-            rows = (torch.arange(B, device=h.device)[:, None] * Sp + mlm_positions).reshape(-1)
+            rows = (row0[:, None] + mlm_positions).reshape(-1)
             tgt = mlm_labels.reshape(-1)
         else:
             rows, tgt = None, None
@@ -529,7 +592,7 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
             if return_logits:
                 out["prediction_logits_masked"] = logits
         # ---- SOP head on [CLS]
-        cls = h.view(B, Sp, -1)[:, 0].contiguous()
+        cls = h.index_select(0, row0) if pk is not None else h.view(B, Sp, -1)[:, 0].contiguous()
         pooled = ops.tanh(ops.linear(cls, f.w("albert.pooler.weight"), f.w("albert.pooler.bias"),
                                      f.g("albert.pooler.weight"), f.g("albert.pooler.bias")))
         if self.training and c.classifier_dropout_prob > 0:
@@ -559,11 +622,17 @@ class AlbertForSequenceClassification(AlbertPreTrainedModel):
         self._add("classifier.weight", self.num_labels, self.config.hidden_size)
         self._add("classifier.bias", self.num_labels, init="zeros")
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, pack_sequences=None,
+                lengths=None):
         c, f = self.config, self.flat
         B = input_ids.shape[0]
-        h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
-        cls = h.view(B, Sp, -1)[:, 0].contiguous()
+        pk = self._packed(pack_sequences, input_ids, attention_mask, token_type_ids, lengths)
+        if pk is not None:
+            h, _ = self.encode(packed=pk)
+            cls = h.index_select(0, pk.row_start)
+        else:
+            h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
+            cls = h.view(B, Sp, -1)[:, 0].contiguous()
         pooled = ops.tanh(ops.linear(cls, f.w("albert.pooler.weight"), f.w("albert.pooler.bias"),
                                      f.g("albert.pooler.weight"), f.g("albert.pooler.bias")))
         if self.training and c.classifier_dropout_prob > 0:
@@ -594,14 +663,26 @@ class AlbertForTokenClassification(AlbertPreTrainedModel):
         self._add("classifier.weight", self.num_labels, self.config.hidden_size)
         self._add("classifier.bias", self.num_labels, init="zeros")
 
-    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None):
+    def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, pack_sequences=None,
+                lengths=None):
         c, f = self.config, self.flat
         B, S = input_ids.shape
-        h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
+        pk = self._packed(pack_sequences, input_ids, attention_mask, token_type_ids, lengths, labels)
+        if pk is not None:
+            h, _ = self.encode(packed=pk)
+        else:
+            h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
         if self.training and c.classifier_dropout_prob > 0:
             h = F.dropout(h, c.classifier_dropout_prob, True)
         logits = ops.linear(h, f.w("classifier.weight"), f.w("classifier.bias"), f.g("classifier.weight"),
                             f.g("classifier.bias"))
+        if pk is not None:
+            # logits come back unpacked as [B, S, labels] (rows of padded positions past a sequence's
+            # slot do not exist: zeros); the loss runs on the packed rows, whose filler carries -100
+            out = {"logits": unpack_rows(logits, pk, S)}
+            if labels is not None:
+                out["loss"] = ops.cross_entropy(logits, pk.extras["labels"])
+            return out
         out = {"logits": logits.view(B, Sp, -1)[:, :S]}
         if labels is not None:
             lab = labels

@@ -190,6 +190,21 @@ def attn_bwd(qkv, mbias, out, dout, lse, H, S, scale, kvinfo=None, dbias=None):
     return attn_composed_bwd(qkv, mbias, out, dout, lse, H, S, scale, dbias)
 
 
+def attn_varlen_fwd(qkv, packed, H, scale):
+    """Fused attention over a packed variable-length batch (``data.packing.PackedBatch``): out
+    [T, H*D] bf16, lse [H, T] fp32 (log2 units).  Only the head sizes in ``FUSED_HEAD_DIMS``: there
+    is no composed path for packed batches, any other head size is an error."""
+    D = qkv.shape[-1] // (3 * H)
+    if D not in FUSED_HEAD_DIMS:
+        raise RuntimeError(f"dedloc_amd: packed batches need a fused attention head size {FUSED_HEAD_DIMS}, "
+                           f"got head_dim {D}")
+    return OPS.attn_varlen_fwd(qkv, packed.seqinfo, packed.seqinfo_host, H, scale)
+
+
+def attn_varlen_bwd(qkv, packed, out, dout, lse, H, scale, dbias=None):
+    return OPS.attn_varlen_bwd(qkv, packed.seqinfo, packed.seqinfo_host, out, dout, lse, H, scale, dbias)
+
+
 class _Attention(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, mbias, H, S, scale):
@@ -233,6 +248,33 @@ class _EmbedLN(torch.autograd.Function):
             ds = OPS.layernorm_bwd(dy.contiguous(), s, gamma, mean, rstd, gg, gb, True)
             OPS.embed_bwd(ds, ids, ctx.tt, gw, gp, gt, ctx.S)
         return (None,) * 15
+
+
+class _EmbedLNPacked(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, anchor, ids, tt, pos, wemb, pemb, temb, gamma, beta, gw, gp, gt, ggamma, gbeta, eps):
+        y, s, mean, rstd = OPS.embed_ln_pos_fwd(ids, tt, pos, wemb, pemb, temb, gamma, beta, eps)
+        ctx.save_for_backward(ids, pos, s, gamma, mean, rstd)
+        ctx.tt = tt
+        ctx.grads = (gw, gp, gt, ggamma, gbeta)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        ids, pos, s, gamma, mean, rstd = ctx.saved_tensors
+        gw, gp, gt, gg, gb = ctx.grads
+        if gw is not None:
+            ds = OPS.layernorm_bwd(dy.contiguous(), s, gamma, mean, rstd, gg, gb, True)
+            OPS.embed_pos_bwd(ds, ids, ctx.tt, pos, gw, gp, gt)
+        return (None,) * 15
+
+
+def embed_layernorm_packed(ids, tt, pos, wemb, pemb, temb, gamma, beta, grads=(None,) * 5, eps=1e-12):
+    """``embed_layernorm`` for a packed batch: ids / tt int64[T], pos int32[T] (each row's offset
+    inside its slot) -> [T, E] bf16."""
+    anchor = torch.empty(0, device=ids.device, requires_grad=True)
+    return _EmbedLNPacked.apply(anchor, ids.contiguous(), None if tt is None else tt.contiguous(), pos.contiguous(),
+                                wemb, pemb, temb, gamma, beta, *grads, eps)
 
 
 def embed_layernorm(ids, tt, wemb, pemb, temb, gamma, beta, grads=(None,) * 5, eps=1e-12):

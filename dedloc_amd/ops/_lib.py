@@ -45,6 +45,11 @@ _SCHEMAS = [
     "attn_fwd(Tensor qkv, Tensor? mbias, int H, int S, float scale, Tensor? kvinfo=None) -> (Tensor, Tensor)",
     "attn_bwd(Tensor qkv, Tensor? mbias, Tensor out, Tensor dout, Tensor lse, int H, int S, float scale, "
     "Tensor? kvinfo=None, Tensor(a!)? dbias=None) -> Tensor",
+    "attn_varlen_fwd(Tensor qkv, Tensor seqinfo, Tensor seqinfo_host, int H, float scale) -> (Tensor, Tensor)",
+    "attn_varlen_bwd(Tensor qkv, Tensor seqinfo, Tensor seqinfo_host, Tensor out, Tensor dout, Tensor lse, int H, "
+    "float scale, Tensor(a!)? dbias=None) -> Tensor",
+    "embed_ln_pos_fwd(Tensor ids, Tensor? tt, Tensor pos, Tensor wemb, Tensor pemb, Tensor temb, Tensor gamma, Tensor beta, float eps) -> (Tensor, Tensor, Tensor, Tensor)",
+    "embed_pos_bwd(Tensor ds, Tensor ids, Tensor? tt, Tensor pos, Tensor(a!) dwemb, Tensor(b!) dpemb, Tensor(c!) dtemb) -> ()",
     "attn_softmax_fwd(Tensor s, Tensor? mbias, int H, float c) -> (Tensor, Tensor)",
     "attn_softmax_bwd(Tensor s, Tensor dp, Tensor? mbias, Tensor lse, Tensor delta, int H, float c, float scale) "
     "-> (Tensor, Tensor)",
@@ -453,6 +458,27 @@ def _embed_bwd_cpu(ds, ids, tt, dwemb, dpemb, dtemb, S):
     dtemb.index_add_(0, tti, g)
 
 
+@_impl("embed_ln_pos_fwd")
+def _embed_pos_fwd_cpu(ids, tt, pos, wemb, pemb, temb, gamma, beta, eps):
+    pos = pos.reshape(-1).long()
+    s = wemb[ids.reshape(-1)] + pemb[pos] + temb[(tt.reshape(-1) if tt is not None else torch.zeros_like(pos))]
+    s_b = _bf(s)
+    sf = s_b.float()
+    mean = sf.mean(-1)
+    rstd = torch.rsqrt(((sf - mean[:, None]) ** 2).mean(-1) + eps)
+    y = (sf - mean[:, None]) * rstd[:, None] * gamma + beta
+    return _bf(y), s_b, mean, rstd
+
+
+@_impl("embed_pos_bwd")
+def _embed_pos_bwd_cpu(ds, ids, tt, pos, dwemb, dpemb, dtemb):
+    g = ds.float().reshape(-1, ds.shape[-1])
+    dwemb.index_add_(0, ids.reshape(-1), g)
+    dpemb.index_add_(0, pos.reshape(-1).long(), g)
+    tti = tt.reshape(-1) if tt is not None else torch.zeros(g.shape[0], dtype=torch.long)
+    dtemb.index_add_(0, tti, g)
+
+
 @_impl("xent_fwd_bwd")
 def _xent_cpu(logits, labels, inplace, ignore_index):
     x = logits.float().reshape(-1, logits.shape[-1])
@@ -515,6 +541,66 @@ def _attn_bwd_cpu(qkv, mbias, out, dout, lse, H, S, scale, kvinfo=None, dbias=No
         HD = H * D
         dbias[:HD] += g[:, :HD].float().sum(0)
         dbias[2 * HD:] += dout.float().reshape(-1, HD).sum(0)
+    return g
+
+
+def packed_layout(seqinfo_host, T):
+    """Validate the packed-batch contract on the host copy of ``seqinfo`` (int32[2B + 1]: B + 1 row
+    offsets, then B key lengths) and return (row offsets, lengths) as Python lists."""
+    v = [int(x) for x in seqinfo_host.reshape(-1).tolist()]
+    if len(v) < 3 or len(v) % 2 == 0:
+        raise RuntimeError("seqinfo must be int32[2B + 1] (B + 1 row offsets, B lengths)")
+    B = (len(v) - 1) // 2
+    rows, lens = v[:B + 1], v[B + 1:]
+    if rows[0] != 0 or rows[B] != T:
+        raise RuntimeError(f"row offsets must run from 0 to T = {T} (got {rows[0]} .. {rows[B]})")
+    for b in range(B):
+        slot = rows[b + 1] - rows[b]
+        if rows[b] % 64 or rows[b + 1] % 64:
+            raise RuntimeError(f"row offset of sequence {b} is not a multiple of 64")
+        if slot < 64 or not 1 <= lens[b] <= slot:
+            raise RuntimeError(f"length {lens[b]} of sequence {b} is outside 1 .. its slot of {slot} rows")
+    return rows, lens
+
+
+def _slot_mbias(slot, n):
+    return torch.where(torch.arange(slot) < n, 0.0, -1.0e30).float().reshape(1, slot)
+
+
+def _check_packed_head_dim(qkv, H, what):
+    D = qkv.shape[-1] // (3 * H)
+    if D not in (64, 128) or qkv.shape[-1] != 3 * H * D:
+        raise RuntimeError(f"dedloc_amd: {what}: head_dim {D} is not supported by the fused attention kernels; "
+                           "supported head sizes are 64 and 128")
+
+
+@_impl("attn_varlen_fwd")
+def _attn_varlen_fwd_cpu(qkv, seqinfo, seqinfo_host, H, scale):
+    """The fixed-S CPU reference run slot by slot (keys past the length masked): out [T, H*D],
+    lse [H, T] in log2 units."""
+    T = qkv.shape[0]
+    _check_packed_head_dim(qkv, H, "attn_varlen_fwd")
+    rows, lens = packed_layout(seqinfo_host, T)
+    out = torch.empty(T, qkv.shape[1] // 3, dtype=qkv.dtype)
+    lse = torch.empty(H, T, dtype=torch.float32)
+    for b, n in enumerate(lens):
+        r0, r1 = rows[b], rows[b + 1]
+        o, l = _attn_fwd_cpu(qkv[r0:r1], _slot_mbias(r1 - r0, n), H, r1 - r0, scale)
+        out[r0:r1] = o
+        lse[:, r0:r1] = l[0]
+    return out, lse
+
+
+@_impl("attn_varlen_bwd")
+def _attn_varlen_bwd_cpu(qkv, seqinfo, seqinfo_host, out, dout, lse, H, scale, dbias=None):
+    T = qkv.shape[0]
+    _check_packed_head_dim(qkv, H, "attn_varlen_bwd")
+    rows, lens = packed_layout(seqinfo_host, T)
+    g = torch.empty_like(qkv)
+    for b, n in enumerate(lens):
+        r0, r1 = rows[b], rows[b + 1]
+        g[r0:r1] = _attn_bwd_cpu(qkv[r0:r1], _slot_mbias(r1 - r0, n), out[r0:r1], dout[r0:r1], None, H, r1 - r0,
+                                 scale, None, dbias)
     return g
 
 

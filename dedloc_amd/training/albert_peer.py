@@ -116,6 +116,7 @@ class AlbertPeer:
                     self.model.resize_token_embeddings(int(json.load(f)["vocab_size"]))
             self.model.materialize(self.device)
             self.model.train()
+            self.model.pack_sequences = bool(getattr(training_args, "pack_sequences", False))
             self.opt, self.scheduler = build_optimizer(self.model, training_args)
         ca = collab_args
         validators, self.local_public_key = make_validators(ca.experiment_prefix)
@@ -177,9 +178,14 @@ class AlbertPeer:
             with self.perf.phase("data"):
                 batch = self.data.next_batch()
             with self.perf.phase("fwd_bwd"):
+                extra = {}
+                if getattr(self.model, "pack_sequences", False):
+                    # host lengths where the stream knows them: packing then needs no device sync
+                    extra["lengths"] = getattr(self.data, "last_lengths", None)
                 out = self.model(batch["input_ids"], batch["attention_mask"], batch["token_type_ids"],
                                  labels=batch.get("labels"), sentence_order_label=batch["sentence_order_label"],
-                                 mlm_positions=batch.get("mlm_positions"), mlm_labels=batch.get("mlm_labels"))
+                                 mlm_positions=batch.get("mlm_positions"), mlm_labels=batch.get("mlm_labels"),
+                                 **extra)
                 loss = out["loss"] / ga if ga > 1 else out["loss"]
                 loss.backward()
             self._loss_sum += loss.detach()
