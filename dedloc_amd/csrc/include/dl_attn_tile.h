@@ -141,6 +141,47 @@ __device__ __forceinline__ void store4(bf16_t* p, float a, float b, float c, flo
   *reinterpret_cast<uint2*>(p) = v;
 }
 
+__device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
+  uint2 v;
+  v.x = (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
+  v.y = (uint32_t)f2bf(c) | ((uint32_t)f2bf(d) << 16);
+  return v;
+}
+
+// Wide store of one 64-column bf16 row held as two 32x32 accumulator tiles (cdna_hip_programming.md
+// T21).  Lane L (hh = 0) holds columns 8k .. 8k+3 of 8-column group k = 4t + v, lane L + 32 columns
+// 8k+4 .. 8k+7 of the same row.  For each pair of groups (k, k+1) a half exchange (vdst = group k,
+// src = group k+1) leaves the lower lane with all 8 columns of group k and the upper lane with all 8
+// of group k+1: one 16-byte store per pair, the upper half 8 elements further on.  Same bytes at
+// the same addresses as 16 store4 calls, in 8 store instructions.  Every lane of the wave must call
+// this (the exchange reads both halves); `live` guards the stores only, and is the same for the two
+// lanes of a row.  `row` = the row's first column, 16-byte aligned.
+__device__ __forceinline__ void store_row64(bf16_t* row, const floatx16 (&x)[2], float scale, int hh, bool live) {
+#pragma unroll
+  for (int t = 0; t < 2; ++t)
+#pragma unroll
+    for (int vp = 0; vp < 2; ++vp) {
+      const int i0 = 8 * vp;
+      uint2 a = pack4(x[t][i0] * scale, x[t][i0 + 1] * scale, x[t][i0 + 2] * scale, x[t][i0 + 3] * scale);
+      uint2 b = pack4(x[t][i0 + 4] * scale, x[t][i0 + 5] * scale, x[t][i0 + 6] * scale, x[t][i0 + 7] * scale);
+      const auto rx = __builtin_amdgcn_permlane32_swap(a.x, b.x, false, false);
+      const auto ry = __builtin_amdgcn_permlane32_swap(a.y, b.y, false, false);
+      if (live) *reinterpret_cast<uint4*>(row + 32 * t + 16 * vp + 8 * hh) = make_uint4(rx[0], ry[0], rx[1], ry[1]);
+    }
+}
+
+// Sum over the 32 lanes of each half-wave (the two halves stay apart): DPP inside each row of 16
+// lanes, then the gfx950 row-pair swap — wave_sum_dpp (dl_common.h) without its last step.  Every
+// lane of a half gets that half's total.
+__device__ __forceinline__ float half_wave_sum(float v) {
+  v += dpp_f32<0xB1>(v);   // lane ^ 1
+  v += dpp_f32<0x4E>(v);   // lane ^ 2
+  v += dpp_f32<0x141>(v);  // row_half_mirror
+  v += dpp_f32<0x140>(v);  // row_mirror
+  const auto r = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+  return __uint_as_float(r[0]) + __uint_as_float(r[1]);  // rows 0+1, 2+3
+}
+
 // The online-softmax rescale of O is deferred until a row's max grows by more than 2^RESCALE_THR
 // (cdna_hip_programming.md T13: P <= 2^8 is exact enough in bf16 for P.V)
 constexpr float RESCALE_THR = 8.f;

@@ -58,8 +58,7 @@ __device__ __forceinline__ void tile_store(const TileRegs& t, uint8_t* tile) {
 // chunk (i & 7) ^ swz(row).  The DMA primitives and the counted waits are in dl_attn_tile.h.
 // Two stages: the next tile's DMA is issued at the top of the current tile and has a whole tile of
 // MFMA / softmax work to land (4 stages measured 1.3% slower forward, 0.5% slower dQ at B=512:
-// profiles/r5_attn_ring_depth_occupancy.jsonl); the dQ epilogue's column-sum scratch (33 KiB)
-// still fits the ring.
+// profiles/r5_attn_ring_depth_occupancy.jsonl).
 constexpr int NBUF = 2;
 constexpr int STAGE = 2 * TILE_BYTES + 512;
 
@@ -320,17 +319,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
 
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
-    if (q[u] < S) {
-      const float inv = 1.f / l[u];
-      bf16_t* op = out + (rb + q[u]) * ldo + h * HD;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-          store4(op + 32 * t + 8 * v + 4 * hh, o[u][t][4 * v] * inv, o[u][t][4 * v + 1] * inv,
-                 o[u][t][4 * v + 2] * inv, o[u][t][4 * v + 3] * inv);
-      if (hh == 0) lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q[u]] = m[u] + log2f(l[u]);
-    }
+    const bool live = q[u] < S;
+    store_row64(out + (rb + q[u]) * ldo + h * HD, o[u], 1.f / l[u], hh, live);
+    if (live && hh == 0) lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q[u]] = m[u] + log2f(l[u]);
   }
 }
 
@@ -347,7 +338,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
                                                              float* __restrict__ delta, bf16_t* __restrict__ dqkv,
                                                              float* __restrict__ dbias, int B, int H, int S_, float sl2,
                                                              float scale, int xcd) {
-  // tail: mask bias / bias-grad partials (the epilogue reuses the first 33 KiB for its column sums)
+  // tail: mask bias (the epilogue reuses the first 2 KiB for the waves' bias-gradient partials)
   __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 4 * 64 * 4];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
@@ -429,7 +420,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
     __syncthreads();
   }
 
-  for (int kt = 0; kt < nt; ++kt) {
+  // One tile body, two instantiations run as consecutive loops (as in the forward), so the masked
+  // form adds no register pressure or branches to the lean one: LEAN for the unmasked tiles
+  // [0, nlean), then the boundary tile of a length mask or every tile of a generic additive mask.
+  // kt keeps counting across the hand-over, so the ring's slot parity (kt % NBUF) and the counted
+  // waits (stages left = nt - 1 - kt) carry over for any nlean in [0, nt].
+  auto tiles = [&](auto lean_tag, int kt0, int kt1) {
+  constexpr bool LEAN = decltype(lean_tag)::value;
+  // the masked form takes its lane coordinates from an opaque copy of the thread index, so its
+  // per-lane LDS addresses and mask operands are formed after the lean loop, not carried through it
+  int tm = threadIdx.x;
+  if constexpr (!LEAN) settle(tm);
+  const int lm = tm & 63, rm = tm & 31, hm = (tm >> 5) & 1;
+  for (int kt = kt0; kt < kt1; ++kt) {
     const uint8_t* Ks;
     const float* mb;
     if constexpr (RING) {
@@ -448,7 +451,6 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
       }
     }
     const uint8_t* Vs = Ks + TILE_BYTES;
-    const bool interior = mb_g == nullptr && (kt + 1) * 64 <= kv_end;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       floatx16 st[QS], dp[QS];
@@ -458,8 +460,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
         for (int i = 0; i < 16; ++i) { st[u][i] = 0.f; dp[u][i] = 0.f; }
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
-        const bf16x8 kfr = lds_row_frag(Ks, 32 * j + r, 2 * ks + hh);
-        const bf16x8 vfr = lds_row_frag(Vs, 32 * j + r, 2 * ks + hh);
+        const bf16x8 kfr = lds_row_frag(Ks, 32 * j + rm, 2 * ks + hm);
+        const bf16x8 vfr = lds_row_frag(Vs, 32 * j + rm, 2 * ks + hm);
 #pragma unroll
         for (int u = 0; u < QS; ++u) {
           st[u] = mfma32(kfr, qf[u][ks], st[u]);
@@ -468,18 +470,23 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
       }
 #pragma unroll
       for (int u = 0; u < QS; ++u) {
-        if (interior) {  // interior tile: no mask
+        if constexpr (LEAN) {  // interior tile: no mask
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const float p = __builtin_amdgcn_exp2f(fmaf(st[u][i], sl2, -l2[u]));
             st[u][i] = p * (dp[u][i] - dl[u]);
           }
-        } else {
+        } else if (mb_g) {  // generic additive bias, staged with the tile
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
-            const int key = kt * 64 + 32 * j + crow(i, hh);
-            const float bias = mb_g ? mb[32 * j + crow(i, hh)] : (key < kv_end ? 0.f : NEG_BIG);
-            const float p = __builtin_amdgcn_exp2f(st[u][i] * sl2 + bias - l2[u]);
+            const float p = __builtin_amdgcn_exp2f(st[u][i] * sl2 + mb[32 * j + crow(i, hm)] - l2[u]);
+            st[u][i] = p * (dp[u][i] - dl[u]);
+          }
+        } else {  // boundary tile of a length mask
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int key = kt * 64 + 32 * j + crow(i, hm);
+            const float p = __builtin_amdgcn_exp2f(st[u][i] * sl2 + (key < kv_end ? 0.f : NEG_BIG) - l2[u]);
             st[u][i] = p * (dp[u][i] - dl[u]);
           }
         }
@@ -491,7 +498,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
         for (int u = 0; u < QS; ++u) pb[u] = pack_acc(st[u], ss);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-          const bf16x8 ktr = tr_operand(Ks, 32 * j + 16 * ss, hh, t, lane);
+          const bf16x8 ktr = tr_operand(Ks, 32 * j + 16 * ss, hm, t, lm);
 #pragma unroll
           for (int u = 0; u < QS; ++u) dq[u][t] = mfma32(ktr, pb[u], dq[u][t]);
         }
@@ -507,78 +514,76 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
       __syncthreads();
     }
   }
+  };
+  const int nlean = mb_g ? 0 : kv_end / 64;
+  tiles(std::true_type{}, 0, nlean);
+  tiles(std::false_type{}, nlean, nt);
   if constexpr (RING) __syncthreads();  // every wave is done with the ring before the epilogue reuses it
+  // The epilogue forms its lane coordinates again from the thread index, behind an opaque copy, so
+  // that none of them stays live across the tile loops (the loops run at the 256-register limit).
+  int tid = threadIdx.x;
+  settle(tid);
+  const int w_ = tid >> 6, r_ = tid & 31, hh_ = (tid >> 5) & 1;
+  int qe[QS];
+#pragma unroll
+  for (int u = 0; u < QS; ++u) qe[u] = bid.x * (128 * QS) + w_ * (32 * QS) + 32 * u + r_;
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
-    if (q[u] < S && hh == 0) delta[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q[u]] = dl[u];
-    if (q[u] < S) {
-      bf16_t* dp_ = dqkv + (rb + q[u]) * ld + h * HD;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int v = 0; v < 4; ++v)
-          store4(dp_ + 32 * t + 8 * v + 4 * hh, dq[u][t][4 * v] * scale, dq[u][t][4 * v + 1] * scale,
-                 dq[u][t][4 * v + 2] * scale, dq[u][t][4 * v + 3] * scale);
-    }
+    const bool live = qe[u] < S;
+    if (live && hh_ == 0) delta[seq_stat<VARLEN>(b, h, H, S, S_, rb) + qe[u]] = dl[u];
+    store_row64(dqkv + (rb + qe[u]) * ld + h * HD, dq[u], scale, hh_, live);
   }
   if (dbias) {
     // Fused bias gradient of the QKV projection (replaces a [T, 3H*64] column-sum pass):
     //   query bias: column sums of the dQ just stored (bf16-rounded, as stored);
     //   value bias: sum_k dV[k] = sum_q dO[q] (softmax rows sum to one), from the dO this block loaded;
     //   key bias:   sum_k dK[k] = 0 exactly (sum_k dS[q,k] = delta - delta), so nothing is added.
-    // Column sums through LDS (cross-lane shuffles of 64 values per lane cost more than the
-    // column-sum pass they replace): per sub-block, each wave writes its [32 queries][64 columns]
-    // fp32 block (16-B chunk c of row r at c ^ (r & 15): conflict-free writes and column reads),
-    // then thread (wave w', column c) sums the 32 rows of wave w' and the four partials meet in
-    // the last 1 KiB.
-    float* red = reinterpret_cast<float*>(smem);          // [4 waves][32 rows][64 columns]
-    float* part = red + 4 * 32 * 64;                       // [4 waves][64 columns]
-    auto chunk_addr = [&](int row, int ch) { return red + (w * 32 + row) * 64 + ((ch ^ (row & 15)) << 2); };
+    // A lane holds 32 dQ and 32 dO columns of its query row(s), and the two half-waves hold
+    // different columns.  So the sums over queries stay in registers: the QS sub-blocks are added
+    // first (rows past S count as zero), then each value is summed over the 32 lanes of its
+    // half-wave (half_wave_sum: DPP + row-pair swap, no LDS).  Lanes 0 and 32 of every wave put the
+    // wave's 2 x 64 column sums in LDS, and after one barrier 128 threads add the four waves'
+    // partials and issue one atomic per column.
+    float* part = reinterpret_cast<float*>(smem);  // [4 waves][dQ 64 | dO 64]
+    float cq[2][16], cd[4][8];
 #pragma unroll
-    for (int u = 0; u < QS; ++u) {
-      const bool live = q[u] < S;
+    for (int t = 0; t < 2; ++t)
 #pragma unroll
-      for (int which = 0; which < 2; ++which) {
-        if (which == 0) {
+      for (int i = 0; i < 16; ++i) {  // dQ column 32 t + 8 (i >> 2) + 4 hh_ + (i & 3), as stored above
+        float v = 0.f;
 #pragma unroll
-          for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int v4 = 0; v4 < 4; ++v4) {  // dQ columns 32 t + 8 v4 + 4 hh + (0..3), as stored above
-              float4 v = float4{0.f, 0.f, 0.f, 0.f};
-              if (live)
-                v = float4{round_bf16(dq[u][t][4 * v4] * scale), round_bf16(dq[u][t][4 * v4 + 1] * scale),
-                           round_bf16(dq[u][t][4 * v4 + 2] * scale), round_bf16(dq[u][t][4 * v4 + 3] * scale)};
-              *reinterpret_cast<float4*>(chunk_addr(r, 8 * t + 2 * v4 + hh)) = v;
-            }
-        } else {
-#pragma unroll
-          for (int ks = 0; ks < 4; ++ks)
-#pragma unroll
-            for (int g = 0; g < 2; ++g) {  // dO columns 16 ks + 8 hh + 4 g + (0..3), as loaded above
-              float4 v = float4{0.f, 0.f, 0.f, 0.f};
-              if (live)
-                v = float4{(float)df[u][ks][4 * g], (float)df[u][ks][4 * g + 1], (float)df[u][ks][4 * g + 2],
-                           (float)df[u][ks][4 * g + 3]};
-              *reinterpret_cast<float4*>(chunk_addr(r, 4 * ks + 2 * hh + g)) = v;
-            }
-        }
-        __syncthreads();
-        {
-          const int c = lane;  // this thread: column c of wave w's 32 rows
-          float sum = 0.f;
-#pragma unroll 8
-          for (int row = 0; row < 32; ++row)
-            sum += red[(w * 32 + row) * 64 + (((c >> 2) ^ (row & 15)) << 2) + (c & 3)];
-          part[w * 64 + c] = sum;
-        }
-        __syncthreads();
-        if (threadIdx.x < 64) {
-          const int c = threadIdx.x;
-          atomicAdd(&dbias[(which ? 2L * H * HD : 0L) + h * HD + c],
-                    part[c] + part[64 + c] + part[128 + c] + part[192 + c]);
-        }
-        __syncthreads();
+        for (int u = 0; u < QS; ++u) v += qe[u] < S ? round_bf16(dq[u][t][i] * scale) : 0.f;
+        cq[t][i] = half_wave_sum(v);
       }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {  // dO column 16 ks + 8 hh_ + e, as loaded above
+        float v = 0.f;
+#pragma unroll
+        for (int u = 0; u < QS; ++u) v += qe[u] < S ? (float)df[u][ks][e] : 0.f;
+        cd[ks][e] = half_wave_sum(v);
+      }
+    if (r_ == 0) {
+      float* pw = part + w_ * 128;
+#pragma unroll
+      for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int v4 = 0; v4 < 4; ++v4)
+          *reinterpret_cast<float4*>(pw + 32 * t + 8 * v4 + 4 * hh_) =
+              float4{cq[t][4 * v4], cq[t][4 * v4 + 1], cq[t][4 * v4 + 2], cq[t][4 * v4 + 3]};
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+        for (int g = 0; g < 2; ++g)
+          *reinterpret_cast<float4*>(pw + 64 + 16 * ks + 8 * hh_ + 4 * g) =
+              float4{cd[ks][4 * g], cd[ks][4 * g + 1], cd[ks][4 * g + 2], cd[ks][4 * g + 3]};
+    }
+    __syncthreads();
+    if (threadIdx.x < 128) {
+      const int c = threadIdx.x & 63, which = threadIdx.x >> 6;  // which: 0 query bias, 1 value bias
+      const float* pc = part + which * 64 + c;
+      atomicAdd(&dbias[(which ? 2L * H * HD : 0L) + h * HD + c], pc[0] + pc[128] + pc[256] + pc[384]);
     }
   }
 }
@@ -782,19 +787,9 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
   }
 #pragma unroll
   for (int u = 0; u < KS; ++u) {
-    if (k[u] < S) {
-      bf16_t* dkp = dqkv + (rb + k[u]) * ld + (long)H * HD + h * HD;
-      bf16_t* dvp = dqkv + (rb + k[u]) * ld + 2L * H * HD + h * HD;
-#pragma unroll
-      for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-          store4(dkp + 32 * t + 8 * v + 4 * hh, dk[u][t][4 * v] * scale, dk[u][t][4 * v + 1] * scale,
-                 dk[u][t][4 * v + 2] * scale, dk[u][t][4 * v + 3] * scale);
-          store4(dvp + 32 * t + 8 * v + 4 * hh, dv[u][t][4 * v], dv[u][t][4 * v + 1], dv[u][t][4 * v + 2],
-                 dv[u][t][4 * v + 3]);
-        }
-    }
+    const bool live = k[u] < S;
+    store_row64(dqkv + (rb + k[u]) * ld + (long)H * HD + h * HD, dk[u], scale, hh, live);
+    store_row64(dqkv + (rb + k[u]) * ld + 2L * H * HD + h * HD, dv[u], 1.f, hh, live);
   }
 }
 
@@ -823,14 +818,15 @@ int dl_attn_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinf
     return dl_attn_hd128_bwd(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, H, S, scale, st);
   if (D != HD || S % 64 != 0 || ld % 8 != 0 || ldo % 8 != 0) return -1;
   const float sl2 = scale * 1.4426950408889634f;
-  // dQ: 2 query sub-blocks per wave with the LDS-DMA ring; dK/dV: one key sub-block per wave with
-  // register staging (the one-wave-per-SIMD 2-sub-block form measured 8% slower, profiles/README.md)
+  // dQ: 2 query sub-blocks per wave with the LDS-DMA ring; dK/dV: one key sub-block per wave, also
+  // through the ring (3.5% faster than register staging at B = 512; the one-wave-per-SIMD
+  // 2-sub-block form measured 8% slower: profiles/README.md)
   dim3 grid_dq((S + 255) / 256, H, B);
   attn_bwd_dq_kernel<true, 2><<<grid_dq, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv,
                                                        dbias, B, H, S, sl2, scale, kAttnXcd);
   dim3 grid_kv((S + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<false, 1><<<grid_kv, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H,
-                                                          S, sl2, scale, kAttnXcd);
+  attn_bwd_dkdv_kernel<true, 1><<<grid_kv, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H,
+                                                         S, sl2, scale, kAttnXcd);
   return 0;
 }
 
@@ -862,7 +858,7 @@ int dl_attn_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf1
   attn_bwd_dq_kernel<true, 2, true><<<grid_dq, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, dout, ldo, lse, delta,
                                                              dqkv, dbias, B, H, T, sl2, scale, kAttnXcd);
   dim3 grid_kv((max_slot + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<false, 1, true><<<grid_kv, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv,
-                                                                B, H, T, sl2, scale, kAttnXcd);
+  attn_bwd_dkdv_kernel<true, 1, true><<<grid_kv, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv,
+                                                               B, H, T, sl2, scale, kAttnXcd);
   return 0;
 }
