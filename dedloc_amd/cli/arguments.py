@@ -68,6 +68,12 @@ class DatasetArguments:
     stream_sources: Optional[str] = field(default=None, metadata={
         "help": "sahajBERT streaming corpus over local text: 'path_a:0.23,path_b:0.77' (tokenized on the fly "
                 "with --tokenizer_path, 10^4-document shuffle buffer, per-peer seed)"})
+    pattern_period: int = field(default=0, metadata={
+        "help": "synthetic data: > 0 makes token rows periodic with this period (learnable; a masked token is "
+                "predictable from its neighbours), 0 keeps independent uniform tokens"})
+    eval_dataset_path: Optional[str] = field(default=None, metadata={
+        "help": "held-out SOP dataset directory (built by data/sop_dataset.py) for --do_eval; without it the "
+                "evaluation runs on a fixed-seed synthetic stream"})
 
 
 @dataclass
@@ -101,6 +107,8 @@ class AlbertTrainingArguments:
     run_name: Optional[str] = None
     dataloader_num_workers: int = 4
     device: Optional[str] = None
+    eval_steps: int = field(default=0, metadata={"help": "with --do_eval: evaluate every this many collaborative steps (0 = only at the end of training)"})
+    eval_max_batches: int = field(default=8, metadata={"help": "with --do_eval: batches of per_device_eval_batch_size per evaluation"})
     pack_sequences: bool = field(default=False, metadata={"help": "run the model on packed, padding-free batches (variable shapes per batch; one device sync per batch when the data stream has no host-side lengths)"})
     # ---- MI355X emulation of the reference's heterogeneous AWS fleet
     throttle: float = field(default=0.0, metadata={"help": "extra idle seconds per training step (emulates a slower peer)"})
@@ -127,3 +135,6 @@ class CoordinatorArguments(BaseTrainingArguments):
     max_runtime: Optional[float] = field(default=None, metadata={"help": "exit after this many seconds"})
     device: Optional[str] = field(default="cpu", metadata={"help": "device for the coordinator's model replica"})
     vocab_size: Optional[int] = field(default=None, metadata={"help": "override the replica's vocabulary size (sahajBERT: 31995)"})
+    do_eval: bool = field(default=False, metadata={"help": "evaluate the replica on held-out data after each saved state (eval_* fields in --metrics_file)"})
+    eval_max_batches: int = field(default=8, metadata={"help": "batches per evaluation"})
+    eval_dataset_path: Optional[str] = field(default=None, metadata={"help": "held-out SOP dataset directory (synthetic fixed-seed stream if absent)"})

@@ -12,7 +12,11 @@
 * every ``save_checkpoint_step_interval`` steps pulls the latest state from the peers and, when
   ``repo_path`` is set and ``upload_interval`` has elapsed, writes the HF checkpoint
   (config.json + pytorch_model.bin) + ``optimizer_state.pt`` there and commits it if the directory
-  is a git repository (push only if a remote exists).
+  is a git repository (push only if a remote exists);
+* with ``--do_eval``, after each successful state load the replica is evaluated on held-out data
+  (training/evaluation.py: ``--eval_dataset_path`` or the fixed-seed synthetic stream, on the
+  replica's device — CPU through the reference ops by default) and the ``eval_*`` fields join that
+  step's line of ``metrics_file``: the collaboration-level held-out curve.
 """
 from __future__ import annotations
 
@@ -60,6 +64,11 @@ class CheckpointHandler:
             client_mode=ca.client_mode, verbose=True, start=False, allow_state_sharing=False,
             peer_id=local_public_key + b"#coordinator", **av)
         self.previous_timestamp = time.time()
+        self.do_eval = bool(getattr(coordinator_args, "do_eval", False))
+        self.eval_max_batches = getattr(coordinator_args, "eval_max_batches", 8)
+        self.eval_dataset_path = getattr(coordinator_args, "eval_dataset_path", None)
+        self.eval_batch_size, self.eval_seq_length = 4, min(512, config.max_position_embeddings)
+        self.last_eval = None  # eval_* fields of the newest saved state (None: not evaluated)
 
     def is_time_to_save_state(self, cur_step):
         if self.save_checkpoint_step_interval is None:
@@ -69,9 +78,24 @@ class CheckpointHandler:
     def save_state(self, cur_step):
         try:
             self.collaborative_optimizer.load_state_from_peers()
+            saved = True
         except ValueError as e:  # a replica that does not match the peers' model: keep hosting the DHT
             logger.error(f"cannot take the peers' state into the coordinator's replica: {e}")
+            saved = False
         self.previous_step = cur_step
+        self.last_eval = self.evaluate() if self.do_eval and saved else None
+
+    def evaluate(self) -> dict:
+        """Held-out statistics of the replica, by the peers' own ``evaluate()``."""
+        from types import SimpleNamespace
+
+        from ..training.evaluation import build_eval_stream, evaluate
+
+        dargs = SimpleNamespace(eval_dataset_path=self.eval_dataset_path)
+        targs = SimpleNamespace(per_device_eval_batch_size=self.eval_batch_size, seq_length=self.eval_seq_length)
+        device = self.model.flat.fp32.device
+        return evaluate(self.model, lambda: build_eval_stream(dargs, targs, self.model.config.vocab_size, device),
+                        self.eval_max_batches)
 
     def is_time_to_upload(self):
         if self.repo_path is None:
@@ -106,6 +130,22 @@ def aggregate(metrics_dict) -> dict:
             "performance": sum(m.samples_per_second for m in metrics)}
 
 
+def record_step(checkpoint_handler: CheckpointHandler, agg: dict, step_changed: bool, metrics_file=None) -> dict:
+    """One aggregated record: save (and, with --do_eval, evaluate) the peers' state when it is due,
+    upload it, and append the record — with that state's ``eval_*`` fields — to ``metrics_file``."""
+    rec = dict(agg, time=time.time())
+    if step_changed and checkpoint_handler.is_time_to_save_state(agg["step"]):
+        checkpoint_handler.save_state(agg["step"])
+        if checkpoint_handler.last_eval is not None:
+            rec.update(checkpoint_handler.last_eval)
+        if checkpoint_handler.is_time_to_upload():
+            checkpoint_handler.upload_checkpoint(agg["loss"])
+    if metrics_file:
+        with open(metrics_file, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+    return rec
+
+
 def main(argv=None):
     parser = HfArgumentParser((CoordinatorArguments, CollaborativeOptimizerArguments, AveragerArguments))
     coordinator_args, collab_optimizer_args, averager_args = parser.parse_args_into_dataclasses(
@@ -134,14 +174,7 @@ def main(argv=None):
                 if step_changed or agg["alive peers"] != alive:
                     logger.info(f"Got metrics from {agg['alive peers']} peers")
                     current_step, alive = agg["step"], agg["alive peers"]
-                    rec = dict(agg, time=time.time())
-                    if coordinator_args.metrics_file:
-                        with open(coordinator_args.metrics_file, "a") as f:
-                            f.write(json.dumps(rec) + "\n")
-                    if step_changed and checkpoint_handler.is_time_to_save_state(current_step):
-                        checkpoint_handler.save_state(current_step)
-                        if checkpoint_handler.is_time_to_upload():
-                            checkpoint_handler.upload_checkpoint(agg["loss"])
+                    record_step(checkpoint_handler, agg, step_changed, coordinator_args.metrics_file)
                     logger.info(f"Step #{current_step}\tloss = {agg['loss']:.5f}\tperformance = "
                                 f"{agg['performance']:.1f} samples/s\talive peers = {agg['alive peers']}")
             logger.debug("Peer is still alive...")

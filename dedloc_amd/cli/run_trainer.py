@@ -1,13 +1,17 @@
 #!/usr/bin/env python
 """GPU trainer peer (albert/run_trainer.py + sahajbert/run_trainer.py equivalent).
 
-    # one peer per GPU; peers of one node share an RCCL world (torchrun-style env):
-    torchrun --nproc-per-node 8 --master-addr 127.0.0.1 -m dedloc_amd.cli.run_trainer \\
+    # one peer per process; LOCAL_RANK picks the GPU and the peer's slot in the heterogeneity profiles:
+    LOCAL_RANK=0 python -m dedloc_amd.cli.run_trainer \\
         --experiment_prefix albert --initial_peers 127.0.0.1:PORT --per_device_train_batch_size 32 ...
 
 Same flags as the reference (HfArgumentParser over the dataclasses in cli/arguments.py).  With
 ``--sahajbert`` the sahajBERT variant applies: initial peers optional, vocabulary 31995, streaming
 variable-length data, metrics published only while synchronized (sahajbert/run_trainer.py:164).
+
+``--do_eval`` evaluates the local model on held-out data (``--eval_dataset_path``, or a fixed-seed
+synthetic stream) every ``--eval_steps`` collaborative steps and at the end of training
+(training/evaluation.py); the sahajBERT streaming corpus has no held-out split, as in the reference.
 """
 from __future__ import annotations
 

@@ -394,6 +394,27 @@ std::tuple<at::Tensor, at::Tensor> xent_fwd_bwd(const at::Tensor& logits, const 
   return {ws.narrow(0, 0, 1).squeeze(0), dl};
 }
 
+// logits: contiguous [..., V], or a 2-D view whose rows are `stride(0)` elements apart (a slice of
+// wider rows is read in place)
+std::tuple<at::Tensor, at::Tensor> xent_eval(const at::Tensor& logits, const at::Tensor& labels,
+                                             int64_t ignore_index) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16, "logits must be a bf16 GPU tensor");
+  expect(labels, at::kLong, "labels");
+  TORCH_CHECK(logits.dim() >= 1 && logits.size(-1) >= 1, "logits must be [..., V] with V >= 1");
+  const int64_t V = logits.size(-1), M = logits.numel() / V;
+  int64_t ld = V;
+  if (logits.dim() == 2 && logits.stride(1) == 1 && logits.stride(0) >= V) ld = logits.stride(0);
+  else TORCH_CHECK(logits.is_contiguous(), "logits must be contiguous or a 2-D view with unit column stride");
+  TORCH_CHECK(labels.numel() == M, "labels has ", labels.numel(), " elements for ", M, " rows of logits");
+  TORCH_CHECK(M <= INT32_MAX && V <= INT32_MAX, "xent_eval: too many rows or columns");
+  auto row_loss = at::empty({M}, logits.options().dtype(at::kFloat));
+  auto row_rank = at::empty({M}, logits.options().dtype(at::kInt));
+  check(dl_xent_eval(cbf(logits), labels.data_ptr<long>(), f32(row_loss), row_rank.data_ptr<int>(), (int)M, (int)V, ld,
+                     (int)ignore_index, cur_stream(logits)),
+        "xent_eval");
+  return {row_loss, row_rank};
+}
+
 // ------------------------------------------------------------------ attention
 inline const int* kvinfo_ptr(const c10::optional<at::Tensor>& kvinfo, int64_t B) {
   if (!kvinfo.has_value()) return nullptr;
@@ -1704,6 +1725,7 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("embed_ln_fwd", &embed_ln_fwd);
   m.impl("embed_bwd", &embed_bwd);
   m.impl("xent_fwd_bwd", &xent_fwd_bwd);
+  m.impl("xent_eval", &xent_eval);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("attn_varlen_fwd", &attn_varlen_fwd);

@@ -534,6 +534,83 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         sd["predictions.decoder.bias"] = sd["predictions.bias"]
         return sd
 
+    def _trunk(self, input_ids, attention_mask, token_type_ids, labels, mlm_positions, pack_sequences, lengths):
+        """Encoder pass of ``forward`` / ``evaluate_batch``: (h, S', PackedBatch or None, row0), row0[b]
+        the row of sequence b's first token in h."""
+        pk = self._packed(pack_sequences, input_ids, attention_mask, token_type_ids, lengths,
+                          labels if mlm_positions is None else None)
+        if pk is not None:
+            h, _ = self.encode(packed=pk)
+            return h, None, pk, pk.row_start  # (b, position) -> row0[b] + position
+        h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
+        return h, Sp, None, torch.arange(input_ids.shape[0], device=h.device) * Sp
+
+    @staticmethod
+    def _mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels):
+        """(rows of h under the MLM head, their targets), or (None, None) without MLM targets."""
+        if mlm_positions is None and labels is not None:
+            if pk is not None:  # packed labels keep the (b, position) order of the rectangular ones
+                flat_lab = pk.extras["labels"]
+                rows = torch.nonzero(flat_lab != -100).squeeze(1)
+                return rows, flat_lab[rows]
+            flat_lab = labels.reshape(-1)
+            pos = torch.nonzero(flat_lab != -100).squeeze(1)
+            b_idx, s_idx = pos // S, pos % S
+            return b_idx * Sp + s_idx, flat_lab[pos]
+        if mlm_positions is not None:
+            return (row0[:, None] + mlm_positions).reshape(-1), mlm_labels.reshape(-1)
+        return None, None
+
+    def _mlm_logits(self, h, rows):
+        c, f = self.config, self.flat
+        hm = h.index_select(0, rows)
+        p = "predictions."
+        t = ops.linear(hm, f.w(p + "dense.weight"), f.w(p + "dense.bias"), f.g(p + "dense.weight"),
+                       f.g(p + "dense.bias"))
+        t = ops.gelu_new(t)
+        t = ops.add_layernorm(t, None, f.p(p + "LayerNorm.weight"), f.p(p + "LayerNorm.bias"),
+                              f.g(p + "LayerNorm.weight"), f.g(p + "LayerNorm.bias"), c.layer_norm_eps)
+        wname = "albert.embeddings.word_embeddings.weight"
+        return ops.linear(t, f.w(wname), f.w(p + "bias"), f.g(wname), f.g(p + "bias"))
+
+    def _sop_logits(self, h, B, Sp, pk, row0):
+        c, f = self.config, self.flat
+        cls = h.index_select(0, row0) if pk is not None else h.view(B, Sp, -1)[:, 0].contiguous()
+        pooled = ops.tanh(ops.linear(cls, f.w("albert.pooler.weight"), f.w("albert.pooler.bias"),
+                                     f.g("albert.pooler.weight"), f.g("albert.pooler.bias")))
+        if self.training and c.classifier_dropout_prob > 0:
+            pooled = F.dropout(pooled, c.classifier_dropout_prob, True)
+        s = "sop_classifier.classifier."
+        return ops.linear(pooled, f.w(s + "weight"), f.w(s + "bias"), f.g(s + "weight"), f.g(s + "bias"))
+
+    def evaluate_batch(self, batch, lengths=None):
+        """Held-out statistics of one batch (a stream's ``next_batch()`` dict), forward only: eval mode
+        and ``no_grad`` (the previous mode is restored), the encoder and head path of ``forward``
+        (``pack_sequences`` and both MLM target forms included) ending in ``ops.eval_cross_entropy``.
+        No gradient buffer is written, no [M, V] gradient is made and no random generator is drawn
+        from.  Returns device scalars: ``mlm_loss_sum``, ``mlm_count``, ``mlm_top1``, ``mlm_top5``,
+        ``sop_loss_sum``, ``sop_count``, ``sop_correct`` (sums and counts, so batches add up)."""
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                ids = batch["input_ids"]
+                B, S = ids.shape
+                labels, pos = batch.get("labels"), batch.get("mlm_positions")
+                h, Sp, pk, row0 = self._trunk(ids, batch.get("attention_mask"), batch.get("token_type_ids"), labels,
+                                              pos, None, lengths)
+                rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, pos, batch.get("mlm_labels"))
+                if rows is None:
+                    raise ValueError("evaluate_batch needs MLM targets: labels or mlm_positions/mlm_labels")
+                mlm = ops.eval_cross_entropy(self._mlm_logits(h, rows), tgt, topk=(1, 5))
+                sop = ops.eval_cross_entropy(self._sop_logits(h, B, Sp, pk, row0), batch["sentence_order_label"],
+                                             topk=(1,))
+        finally:
+            self.train(was_training)
+        return {"mlm_loss_sum": mlm["loss_sum"], "mlm_count": mlm["count"], "mlm_top1": mlm["top1"],
+                "mlm_top5": mlm["top5"], "sop_loss_sum": sop["loss_sum"], "sop_count": sop["count"],
+                "sop_correct": sop["top1"]}
+
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, sentence_order_label=None,
                 mlm_positions=None, mlm_labels=None, return_logits=False, pack_sequences=None, lengths=None):
         """HF-compatible pre-training forward.
@@ -546,59 +623,22 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         padding-free token buffer; ``lengths`` are the rows' host-side lengths (without them one
         device synchronisation reads them from ``attention_mask``).  Inputs and ``out`` are unchanged.
         """
-        c, f = self.config, self.flat
         B, S = input_ids.shape
-        pk = self._packed(pack_sequences, input_ids, attention_mask, token_type_ids, lengths,
-                          labels if mlm_positions is None else None)
-        if pk is not None:
-            h, _ = self.encode(packed=pk)
-            row0 = pk.row_start  # first row of each sequence: (b, position) -> row0[b] + position
-        else:
-            h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
-            row0 = torch.arange(B, device=h.device) * Sp
+        h, Sp, pk, row0 = self._trunk(input_ids, attention_mask, token_type_ids, labels, mlm_positions,
+                                      pack_sequences, lengths)
         out = {}
         # ---- MLM head on masked positions only
-        if mlm_positions is None and labels is not None:
-            if pk is not None:  # packed labels keep the (b, position) order of the rectangular ones
-                flat_lab = pk.extras["labels"]
-                rows = torch.nonzero(flat_lab != -100).squeeze(1)
-                tgt = flat_lab[rows]
-            else:
-                flat_lab = labels.reshape(-1)
-                pos = torch.nonzero(flat_lab != -100).squeeze(1)
-                b_idx, s_idx = pos // S, pos % S
-                rows = b_idx * Sp + s_idx
-                tgt = flat_lab[pos]
-        elif mlm_positions is not None:
-            P = mlm_positions.shape[1]
-            rows = (row0[:, None] + mlm_positions).reshape(-1)
-            tgt = mlm_labels.reshape(-1)
-        else:
-            rows, tgt = None, None
+        rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels)
         loss = None
         if rows is not None:
-            hm = h.index_select(0, rows)
-            p = "predictions."
-            t = ops.linear(hm, f.w(p + "dense.weight"), f.w(p + "dense.bias"), f.g(p + "dense.weight"),
-                           f.g(p + "dense.bias"))
-            t = ops.gelu_new(t)
-            t = ops.add_layernorm(t, None, f.p(p + "LayerNorm.weight"), f.p(p + "LayerNorm.bias"),
-                                  f.g(p + "LayerNorm.weight"), f.g(p + "LayerNorm.bias"), c.layer_norm_eps)
-            wname = "albert.embeddings.word_embeddings.weight"
-            logits = ops.linear(t, f.w(wname), f.w(p + "bias"), f.g(wname), f.g(p + "bias"))
+            logits = self._mlm_logits(h, rows)
             mlm_loss = ops.cross_entropy(logits, tgt)
             out["mlm_loss"] = mlm_loss
             loss = mlm_loss
             if return_logits:
                 out["prediction_logits_masked"] = logits
         # ---- SOP head on [CLS]
-        cls = h.index_select(0, row0) if pk is not None else h.view(B, Sp, -1)[:, 0].contiguous()
-        pooled = ops.tanh(ops.linear(cls, f.w("albert.pooler.weight"), f.w("albert.pooler.bias"),
-                                     f.g("albert.pooler.weight"), f.g("albert.pooler.bias")))
-        if self.training and c.classifier_dropout_prob > 0:
-            pooled = F.dropout(pooled, c.classifier_dropout_prob, True)
-        s = "sop_classifier.classifier."
-        sop_logits = ops.linear(pooled, f.w(s + "weight"), f.w(s + "bias"), f.g(s + "weight"), f.g(s + "bias"))
+        sop_logits = self._sop_logits(h, B, Sp, pk, row0)
         out["sop_logits"] = sop_logits
         if sentence_order_label is not None:
             sop_loss = ops.cross_entropy(sop_logits, sentence_order_label)

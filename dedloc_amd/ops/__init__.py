@@ -312,8 +312,26 @@ def cross_entropy(logits, labels, ignore_index=-100):
     return _CrossEntropy.apply(logits.contiguous(), labels.reshape(-1).contiguous(), ignore_index)
 
 
+@torch.no_grad()
+def eval_cross_entropy(logits, labels, ignore_index=-100, topk=(1, 5)):
+    """Evaluation cross-entropy over rows whose label != ignore_index, forward only (the
+    ``xent_eval`` kernel: one read of the logits, no gradient).  Returns device scalars
+    ``loss_sum`` (fp64 sum of the per-row losses), ``count`` (int64) and one ``top{k}`` (int64 number
+    of rows whose label ranks below k; ties go to the lower index).  The per-row outputs are
+    reduced by plain ``sum`` — a fixed order, so two calls agree bitwise — and nothing is read back."""
+    if not (logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]):
+        logits = logits.contiguous()
+    row_loss, row_rank = OPS.xent_eval(logits, labels.reshape(-1).contiguous(), ignore_index)
+    valid = row_rank >= 0
+    out = {"loss_sum": row_loss.sum(dtype=torch.float64), "count": valid.sum()}
+    for k in topk:
+        out[f"top{k}"] = (valid & (row_rank < k)).sum()
+    return out
+
+
 __all__ = [
-    "linear", "gelu_new", "tanh", "add_layernorm", "attention", "embed_layernorm", "cross_entropy", "OPS",
+    "linear", "gelu_new", "tanh", "add_layernorm", "attention", "embed_layernorm", "cross_entropy",
+    "eval_cross_entropy", "OPS",
     "load_native", "native_loaded",
 ]
 

@@ -42,6 +42,7 @@ _SCHEMAS = [
     "embed_ln_fwd(Tensor ids, Tensor? tt, Tensor wemb, Tensor pemb, Tensor temb, Tensor gamma, Tensor beta, int S, float eps) -> (Tensor, Tensor, Tensor, Tensor)",
     "embed_bwd(Tensor ds, Tensor ids, Tensor? tt, Tensor(a!) dwemb, Tensor(b!) dpemb, Tensor(c!) dtemb, int S) -> ()",
     "xent_fwd_bwd(Tensor logits, Tensor labels, bool inplace, int ignore_index) -> (Tensor, Tensor)",
+    "xent_eval(Tensor logits, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
     "attn_fwd(Tensor qkv, Tensor? mbias, int H, int S, float scale, Tensor? kvinfo=None) -> (Tensor, Tensor)",
     "attn_bwd(Tensor qkv, Tensor? mbias, Tensor out, Tensor dout, Tensor lse, int H, int S, float scale, "
     "Tensor? kvinfo=None, Tensor(a!)? dbias=None) -> Tensor",
@@ -498,6 +499,25 @@ def _xent_cpu(logits, labels, inplace, ignore_index):
         logits.copy_(g)
         g = logits
     return loss.float(), g
+
+
+@_impl("xent_eval")
+def _xent_eval_cpu(logits, labels, ignore_index):
+    """Per row: loss = logsumexp(x) - x[label] (fp32) and rank = #{j : x[j] > x[label] or
+    (x[j] == x[label] and j < label)} (int32) on the bf16 values; ignored rows are (0, -1)."""
+    V = logits.shape[-1]
+    x = logits.float().reshape(-1, V)
+    lab = labels.reshape(-1)
+    valid = (lab != ignore_index) & (lab >= 0) & (lab < V)
+    safe = torch.where(valid, lab, torch.zeros_like(lab))
+    xl = x.gather(1, safe[:, None])
+    col = torch.arange(V, device=x.device)[None, :]
+    rank = ((x > xl) | ((x == xl) & (col < safe[:, None]))).sum(1)
+    loss = torch.logsumexp(x, -1) - xl.squeeze(1)
+    # a label outside the row (and not ignore_index) is never used as an index: (nan, -1)
+    loss = torch.where(valid, loss, torch.where(lab == ignore_index, 0.0, float("nan")).float())
+    rank = torch.where(valid, rank, torch.full_like(rank, -1))
+    return loss.float(), rank.to(torch.int32)
 
 
 def _attn_probs(qkv, mbias, H, S, scale):

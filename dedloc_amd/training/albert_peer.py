@@ -154,7 +154,12 @@ class AlbertPeer:
             self.data = SyntheticSOPStream(training_args.per_device_train_batch_size, training_args.seq_length,
                                            self.model.config.vocab_size, seed=seed, device=self.device,
                                            mask_mode=getattr(dataset_args, "mask_mode", "fixed"),
-                                           length_mode=getattr(dataset_args, "length_mode", "full"))
+                                           length_mode=getattr(dataset_args, "length_mode", "full"),
+                                           pattern_period=getattr(dataset_args, "pattern_period", 0))
+        # --do_eval: held-out evaluation every eval_steps collaborative steps and at the end of train()
+        self.do_eval = bool(getattr(training_args, "do_eval", False)) and impl != "eager"
+        self.eval_log = []
+        self._last_eval_step = None
         flat = self.model.flat
         self._clip_part = torch.zeros(256, device=self.device)
         self._clip_out = torch.zeros(3, device=self.device)  # [norm, finite, 1 - finite]
@@ -206,9 +211,43 @@ class AlbertPeer:
         self._pace()
         self.throttle.end()
         self.on_step_end()
+        if self.do_eval and self._eval_due():
+            self.evaluate()
         ev = self.churn.due(self.collab_opt.local_step, time.time())
         if ev is not None:
             self.drop_out(ev.duration, restart=ev.mode == "restart")
+
+    # ------------------------------------------------------------------ held-out evaluation
+    def _eval_due(self) -> bool:
+        every, step = int(getattr(self.args, "eval_steps", 0) or 0), self.collab_opt.local_step
+        return every > 0 and step > 0 and step % every == 0 and step != self._last_eval_step
+
+    def evaluate(self) -> Dict:
+        """One evaluation of the local model (training/evaluation.py) at the current collaborative
+        step: logged, kept in ``eval_log`` and appended to ``metrics_file`` as its own JSONL line with
+        ``"eval": true``.  The time it takes is kept out of the throughput estimate the
+        collaboration's ETA is computed from; the training stream and every random generator of the
+        training loop are left as they were."""
+        from .evaluation import build_eval_stream, evaluate
+
+        co = self.collab_opt
+        self._last_eval_step = co.local_step
+        with co.performance_ema.pause():
+            res = evaluate(self.model,
+                           lambda: build_eval_stream(self.dargs, self.args, self.model.config.vocab_size, self.device),
+                           getattr(self.args, "eval_max_batches", 8))
+            timer = getattr(co, "_device_timer", None)
+            if timer is not None:  # GPU peers time micro-steps on the device: restart that clock too
+                timer.resume()
+        rec = dict(res, eval=True, step=int(co.local_step), hf_step=self.hf_step, time=time.time())
+        logger.info(f"Evaluation at step {rec['step']}: loss {res['eval_loss']:.5f} (mlm {res['eval_mlm_loss']:.5f}, "
+                    f"sop {res['eval_sop_loss']:.5f}), mlm accuracy {res['eval_mlm_accuracy']:.4f} "
+                    f"(top-5 {res['eval_mlm_top5']:.4f}), sop accuracy {res['eval_sop_accuracy']:.4f}")
+        self.eval_log.append(rec)
+        if self.args.metrics_file:
+            with open(self.args.metrics_file, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+        return rec
 
     def _pace(self):
         """Keep the host at most one micro-step ahead of the GPU: wait for the PREVIOUS step's end
@@ -335,6 +374,8 @@ class AlbertPeer:
             if max_seconds is not None and time.time() - t0 > max_seconds:
                 break
         self.flush_metrics(block=True)
+        if self.do_eval and self._last_eval_step != self.collab_opt.local_step:
+            self.evaluate()
 
     def shutdown(self):
         try:
