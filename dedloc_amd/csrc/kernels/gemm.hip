@@ -291,7 +291,9 @@ int dl_gemm(int a_kouter, int b_kouter, int epi, const bf16_t* A, long lda, cons
   if (a_kouter && M % BM) return -1;
   if (b_kouter && N % BN) return -1;
   if (splits < 1) splits = 1;
-  while (splits > 1 && (K / splits) % BK) --splits;
+  // the splits must tile K exactly, in whole K-tiles: splits * k_per_split == K.  (K / splits) % BK
+  // alone lets K = 66624, splits = 65 through (1024 rows per split) and drops the last 64 rows.
+  while (splits > 1 && K % (splits * BK)) --splits;
   GemmArgs a{A, lda, B, ldb, M, N, K, C, ldc, Cf, ldcf, bias, R, ldr, H, ldh, dbias, K / splits};
 #define DL_GEMM_CASE(AK, BK_, E) \
   if (a_kouter == AK && b_kouter == BK_ && epi == E) return launch<AK, BK_, E>(a, splits, st);
