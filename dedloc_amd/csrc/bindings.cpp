@@ -1048,6 +1048,31 @@ at::Tensor multicrop(const at::Tensor& pool, const at::Tensor& params, int64_t s
   return out;
 }
 
+at::Tensor multicrop_ragged(const at::Tensor& bytes, const at::Tensor& meta, const at::Tensor& params, int64_t size,
+                            int64_t rad, at::ArrayRef<double> mean, at::ArrayRef<double> std) {
+  expect(bytes, at::kByte, "bytes");
+  expect(meta, at::kLong, "meta");
+  expect(params, at::kFloat, "params");
+  TORCH_CHECK(bytes.dim() == 1 && bytes.numel() > 0, "bytes must be a non-empty 1-D buffer");
+  TORCH_CHECK(meta.dim() == 2 && meta.size(1) == 3 && meta.size(0) > 0, "meta must be [n > 0, 3] (offset, H, W)");
+  TORCH_CHECK(params.dim() == 2 && params.size(1) == 20, "params must be [nb, 20]");
+  TORCH_CHECK(meta.get_device() == bytes.get_device() && params.get_device() == bytes.get_device(),
+              "bytes, meta and params must be on one device");
+  TORCH_CHECK(mean.size() == 3 && std.size() == 3, "mean/std need 3 channels");
+  TORCH_CHECK(size > 0 && size <= 4096, "crop size must be in [1, 4096]");
+  const int64_t nb = params.size(0), S = size;
+  auto out = at::empty({nb, 3, S, S}, params.options().dtype(at::kBFloat16), at::MemoryFormat::ChannelsLast);
+  if (nb == 0) return out;
+  auto ws = at::empty({nb * 3 * S * S + nb}, params.options());
+  const float m[3] = {(float)mean[0], (float)mean[1], (float)mean[2]};
+  const float sd[3] = {(float)std[0], (float)std[1], (float)std[2]};
+  check(dl_multicrop_ragged(bytes.data_ptr<uint8_t>(), (long)bytes.numel(), meta.data_ptr<int64_t>(),
+                            (int)meta.size(0), f32(params), (int)nb, (int)S, (int)rad, m, sd, f32(ws), bf(out),
+                            cur_stream(bytes)),
+        "multicrop_ragged (blur radius must be < crop size and <= 16)");
+  return out;
+}
+
 // ------------------------------------------------------------------ BatchNorm (channels-last, fused act)
 inline void expect_nhwc(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be a GPU tensor");
@@ -1727,6 +1752,7 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("l2norm_fwd", &l2norm_fwd);
   m.impl("l2norm_bwd", &l2norm_bwd);
   m.impl("multicrop", &multicrop);
+  m.impl("multicrop_ragged", &multicrop_ragged);
   m.impl("layernorm_fwd", &layernorm_fwd);
   m.impl("layernorm_bwd", &layernorm_bwd);
   m.impl("gelu_fwd", &gelu_fwd);

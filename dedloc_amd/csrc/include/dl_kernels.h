@@ -127,6 +127,11 @@ int dl_row_normalize(float* w, int rows, int d, hipStream_t st);
 // ws >= 2 * nb*3*S*S + nb floats, out [nb, S, S, 3] bf16 (channels-last [nb, 3, S, S])
 int dl_multicrop(const float* pool, int P, int Hp, int Wp, const float* params, int nb, int S, int rad, const float* mean,
                  const float* stdv, float* ws, bf16_t* out, hipStream_t st);
+// ... from a ragged batch of uint8 HWC RGB images packed back to back in bytes [nbytes] (no
+// alignment), meta [n, 3] int64 rows (byte offset, H, W), params [nb, 20] with columns 0-4 =
+// (meta row, box left, box top, box width (negative: mirrored), box height); ws and out as above
+int dl_multicrop_ragged(const unsigned char* bytes, long nbytes, const long* meta, int n, const float* params, int nb,
+                        int S, int rad, const float* mean, const float* stdv, float* ws, bf16_t* out, hipStream_t st);
 int dl_bn_fwd(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* gamma, const float* beta, float* sums,
               float* mean, float* rstd, float* run_mean, float* run_var, long R, int C, int G, float eps,
               float momentum, int relu, hipStream_t st, int sums_zeroed = 0, int stats_ready = 0);

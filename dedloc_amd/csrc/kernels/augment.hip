@@ -13,6 +13,14 @@
 //
 // Parameter row: 0 src image, 1-4 affine (ax, cx, ay, cy), 5 brightness, 6 contrast, 7 saturation,
 // 8 colour applied, 9 grayscale, 10-18 hue matrix (row-major), 19 blur sigma.
+//
+// Ragged source (dl_multicrop_ragged: real images of different sizes, data/image_folder.py): the
+// batch's uint8 HWC RGB images lie back to back in one byte buffer (no alignment padding) with an
+// int64 [n, 3] table of (byte offset, H, W); `sample_ragged` replaces `sample` and resamples each
+// RandomResizedCrop box with PIL's area-aware (antialiased) bilinear filter, crop first, then
+// resize; color_blur_norm runs unchanged on its output.  Parameter row for the ragged source,
+// integers stored as floats: 0 row of the image table, 1 box left j, 2 box top i, 3 box width w in
+// pixels (negative: mirrored), 4 box height h; 5-19 as above.
 #include "dl_common.h"
 #include "dl_kernels.h"
 
@@ -60,6 +68,84 @@ __global__ __launch_bounds__(256) void mc_sample_kernel(const float* __restrict_
     for (int c = 0; c < 3; ++c) {
       const float* s = src + c * plane;
       v[c] = w00 * s[y0 * Wp + x0] + w01 * s[y0 * Wp + x1] + w10 * s[y1 * Wp + x0] + w11 * s[y1 * Wp + x1];
+      out[((size_t)i * 3 + c) * S * S + p] = v[c];
+    }
+    l = lum(v[0], v[1], v[2]);
+  }
+  l = block_sum(l, red);
+  if (threadIdx.x == 0) atomicAdd(lumsum + i, l);
+}
+
+// One axis of the antialiased bilinear resize of an n_in-pixel box to S pixels, for output index o:
+// taps [lo, hi) of the box and the centre c and 1 / support of the triangle weight
+// max(0, 1 - |x + 0.5 - c| / sup) (PIL's BILINEAR filter, the same taps and weights as
+// F.interpolate(mode="bilinear", antialias=True, align_corners=False)).
+__device__ __forceinline__ void tri_taps(int o, int n_in, int S, int& lo, int& hi, float& c, float& rsup) {
+  const float scale = (float)n_in / (float)S;
+  const float sup = fmaxf(scale, 1.f);
+  c = ((float)o + 0.5f) * scale;
+  lo = max(0, (int)(c - sup + 0.5f));
+  hi = min(n_in, (int)(c + sup + 0.5f));
+  hi = max(hi, lo + 1);  // never an empty tap set (lo < n_in: c < n_in and sup >= 0.5)
+  rsup = 1.f / sup;
+}
+
+__device__ __forceinline__ int f2i(float v) { return (int)fminf(fmaxf(v, -1.0e9f), 1.0e9f); }  // NaN -> -1e9
+
+// RandomResizedCrop + flip of a ragged uint8 batch: one thread per output pixel runs the separable
+// triangle filter over its taps of the crop box directly (run-time tap counts: ~scale + 1 per axis,
+// no fixed maximum).  Neighbouring threads are neighbouring output columns, so their taps are
+// neighbouring (overlapping) source bytes of the same rows and the re-reads stay in L1 / L2.
+// Every quantity read from the tables is clamped (image row, offset, H, W, box), and every byte
+// address is clamped to [0, nbytes): a bad row can never read out of bounds.
+__global__ __launch_bounds__(256) void mc_sample_ragged_kernel(const unsigned char* __restrict__ bytes, long nbytes,
+                                                                const long* __restrict__ meta, int n,
+                                                                const float* __restrict__ prm, int S,
+                                                                float* __restrict__ out, float* __restrict__ lumsum) {
+  __shared__ float red[16];
+  const int i = blockIdx.y;
+  const int p = blockIdx.x * blockDim.x + threadIdx.x;
+  const float* pr = prm + (size_t)i * NP;
+  const long* mt = meta + (size_t)min(max(f2i(pr[0]), 0), n - 1) * 3;
+  const long last = nbytes - 1;
+  const long off = min(max(mt[0], 0L), last);
+  // an image cannot be larger than the buffer: bounds W, H (and with them every tap loop) and
+  // keeps the address arithmetic far from overflow
+  const int W = (int)min(max(mt[2], 1L), max(min(nbytes / 3, 1L << 24), 1L));
+  const int H = (int)min(max(mt[1], 1L), max(min(nbytes / (3L * W), 1L << 24), 1L));
+  const float wf = pr[3];
+  const int w = min(max(f2i(fabsf(wf)), 1), W), h = min(max(f2i(pr[4]), 1), H);
+  const int j = min(max(f2i(pr[1]), 0), W - w), i0 = min(max(f2i(pr[2]), 0), H - h);
+  float l = 0.f;
+  if (p < S * S) {
+    const float rS = 1.f / (float)S;
+    const int yy = fdiv(p, S, rS), xx = p - yy * S;
+    int xlo, xhi, ylo, yhi;
+    float cx, cy, rsx, rsy;
+    tri_taps(wf < 0.f ? S - 1 - xx : xx, w, S, xlo, xhi, cx, rsx);
+    tri_taps(yy, h, S, ylo, yhi, cy, rsy);
+    float acc[3] = {0.f, 0.f, 0.f};
+    float wys = 0.f, wxs = 0.f;
+    for (int x = xlo; x < xhi; ++x) wxs += fmaxf(0.f, 1.f - fabsf((float)x + 0.5f - cx) * rsx);
+    for (int y = ylo; y < yhi; ++y) {
+      const float wy = fmaxf(0.f, 1.f - fabsf((float)y + 0.5f - cy) * rsy);
+      wys += wy;
+      const long row = off + ((long)(i0 + y) * W + j) * 3;
+      float r[3] = {0.f, 0.f, 0.f};
+      for (int x = xlo; x < xhi; ++x) {
+        const float wx = fmaxf(0.f, 1.f - fabsf((float)x + 0.5f - cx) * rsx);
+        const long a = row + (long)x * 3;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) r[c] += wx * (float)bytes[min(a + c, last)];
+      }
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[c] += wy * r[c];
+    }
+    const float nrm = 1.f / (255.f * wxs * wys);
+    float v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      v[c] = acc[c] * nrm;
       out[((size_t)i * 3 + c) * S * S + p] = v[c];
     }
     l = lum(v[0], v[1], v[2]);
@@ -165,21 +251,13 @@ __global__ __launch_bounds__(256) void mc_color_blur_norm_kernel(const float* __
   }
 }
 
-}  // namespace
-
-int dl_multicrop(const float* pool, int P, int Hp, int Wp, const float* params, int nb, int S, int rad, const float* mean,
-                 const float* stdv, float* ws, bf16_t* out, hipStream_t st) {
-  if (rad < 0 || rad > MAX_RAD || rad >= S || nb <= 0) return -1;
-  const size_t img = (size_t)nb * 3 * S * S;
-  float* a = ws;
-  float* lumsum = ws + img;
-  // band height: the two fp16 band images within ~56 KiB of LDS (a light co-tenant of the trunk's
-  // kernels, which run concurrently with the data prefetch)
+// colour + blur + normalize over the sampled planes `a` (ws), shared by both sources.
+// band height: the two fp16 band images within ~56 KiB of LDS (a light co-tenant of the trunk's
+// kernels, which run concurrently with the data prefetch)
+int color_blur_norm(const float* a, const float* lumsum, const float* params, int nb, int S, int rad, const float* mean,
+                    const float* stdv, bf16_t* out, hipStream_t st) {
   const int T = std::max(1, std::min(32, (56 * 1024) / (12 * S) - 2 * rad));
   const size_t lds = sizeof(_Float16) * 2 * 3 * (size_t)(T + 2 * rad) * S;
-  if (lds > 150 * 1024) return -1;
-  DL_HIP_CHECK(hipMemsetAsync(lumsum, 0, sizeof(float) * nb, st));
-  mc_sample_kernel<<<dim3((S * S + 255) / 256, nb), 256, 0, st>>>(pool, P, Hp, Wp, params, S, a, lumsum);
   static bool attr = false;
   if (!attr) {
     DL_HIP_CHECK(hipFuncSetAttribute((const void*)mc_color_blur_norm_kernel,
@@ -189,4 +267,32 @@ int dl_multicrop(const float* pool, int P, int Hp, int Wp, const float* params, 
   mc_color_blur_norm_kernel<<<dim3((S + T - 1) / T, nb), 256, lds, st>>>(
       a, out, S, T, params, lumsum, rad, mean[0], mean[1], mean[2], 1.f / stdv[0], 1.f / stdv[1], 1.f / stdv[2]);
   return 0;
+}
+
+bool bad_shape(int nb, int S, int rad) {
+  if (rad < 0 || rad > MAX_RAD || rad >= S || nb <= 0) return true;
+  const int T = std::max(1, std::min(32, (56 * 1024) / (12 * S) - 2 * rad));
+  return sizeof(_Float16) * 2 * 3 * (size_t)(T + 2 * rad) * S > 150 * 1024;
+}
+
+}  // namespace
+
+int dl_multicrop(const float* pool, int P, int Hp, int Wp, const float* params, int nb, int S, int rad, const float* mean,
+                 const float* stdv, float* ws, bf16_t* out, hipStream_t st) {
+  if (bad_shape(nb, S, rad)) return -1;
+  float* a = ws;
+  float* lumsum = ws + (size_t)nb * 3 * S * S;
+  DL_HIP_CHECK(hipMemsetAsync(lumsum, 0, sizeof(float) * nb, st));
+  mc_sample_kernel<<<dim3((S * S + 255) / 256, nb), 256, 0, st>>>(pool, P, Hp, Wp, params, S, a, lumsum);
+  return color_blur_norm(a, lumsum, params, nb, S, rad, mean, stdv, out, st);
+}
+
+int dl_multicrop_ragged(const unsigned char* bytes, long nbytes, const long* meta, int n, const float* params, int nb,
+                        int S, int rad, const float* mean, const float* stdv, float* ws, bf16_t* out, hipStream_t st) {
+  if (bad_shape(nb, S, rad) || nbytes <= 0 || n <= 0) return -1;
+  float* a = ws;
+  float* lumsum = ws + (size_t)nb * 3 * S * S;
+  DL_HIP_CHECK(hipMemsetAsync(lumsum, 0, sizeof(float) * nb, st));
+  mc_sample_ragged_kernel<<<dim3((S * S + 255) / 256, nb), 256, 0, st>>>(bytes, nbytes, meta, n, params, S, a, lumsum);
+  return color_blur_norm(a, lumsum, params, nb, S, rad, mean, stdv, out, st);
 }

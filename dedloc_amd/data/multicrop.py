@@ -13,6 +13,10 @@ the augmentation itself is ``torch.ops.dedloc.multicrop`` — four HIP kernels p
 GPU (csrc/kernels/augment.hip: bilinear RandomResizedCrop+flip, colour jitter + grayscale, separable
 Gaussian blur, Normalize + bf16 channels-last store) and ``augment_reference`` (plain tensor ops) on
 the CPU and as the numerics reference.  The host never decodes or transforms JPEGs.
+Real images (``DATA_SOURCES: [disk_folder]``, data/image_folder.py) are decoded on the host and
+nothing more: a ragged uint8 batch goes through ``torch.ops.dedloc.multicrop_ragged`` (boxes drawn
+in pixels by ``sample_params_ragged``, PIL's area-aware bilinear filter on the GPU) and
+``augment_reference_ragged``; colour, blur and normalize are the same code for both sources.
 Differences from the PIL path: ColorJitter applies its four ops in a fixed order (torchvision
 permutes them) and hue is rotated in YIQ space.
 """
@@ -53,6 +57,13 @@ def augment_reference(pool: torch.Tensor, params: torch.Tensor, size: int, rad: 
     theta[:, 0, 0], theta[:, 0, 2], theta[:, 1, 1], theta[:, 1, 2] = prm[:, 1], prm[:, 2], prm[:, 3], prm[:, 4]
     grid = F.affine_grid(theta, [nb, 3, size, size], align_corners=False)
     x = F.grid_sample(src, grid, mode="bilinear", padding_mode="border", align_corners=False)
+    return _color_blur_norm(x, prm, size, rad, mean, std)
+
+
+def _color_blur_norm(x: torch.Tensor, prm: torch.Tensor, size: int, rad: int, mean, std) -> torch.Tensor:
+    """Colour jitter, grayscale, Gaussian blur, Normalize and the bf16 channels-last cast over the
+    sampled crops ``x`` [nb, 3, size, size] (table columns 5-19): the tail both sources share."""
+    nb, dev = prm.shape[0], x.device
     lum_w = torch.tensor(_LUM, device=dev).view(1, 3, 1, 1)
 
     def col(k):
@@ -80,6 +91,36 @@ def augment_reference(pool: torch.Tensor, params: torch.Tensor, size: int, rad: 
     return x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
 
 
+def crop_resize_ragged(data: torch.Tensor, meta: torch.Tensor, params: torch.Tensor, size: int) -> torch.Tensor:
+    """Stage 1 of ``dedloc::multicrop_ragged`` in tensor ops: per table row, crop the box from its
+    uint8 HWC image, resize it with the antialiased bilinear filter (PIL's BILINEAR), mirror:
+    [nb, 3, size, size] fp32 in [0, 1].  Rows are clamped as the kernel clamps them."""
+    prm, nbytes, n = params.float(), data.numel(), meta.shape[0]
+    out = []
+    for row in prm[:, :5].tolist():
+        r = [int(v) if math.isfinite(v) else -10 ** 9 for v in row]
+        off, H, W = (int(v) for v in meta[min(max(r[0], 0), n - 1)])
+        off = min(max(off, 0), nbytes - 1)
+        W = min(max(W, 1), max(nbytes // 3, 1))
+        H = min(max(H, 1), max(nbytes // (3 * W), 1))
+        w, h = min(max(abs(r[3]), 1), W), min(max(r[4], 1), H)
+        j, i = min(max(r[1], 0), W - w), min(max(r[2], 0), H - h)
+        idx = (off + torch.arange(H * W * 3, device=data.device)).clamp_(max=nbytes - 1)
+        img = data[idx].view(H, W, 3)[i:i + h, j:j + w].permute(2, 0, 1).float().div(255).unsqueeze(0)
+        c = F.interpolate(img, size=(size, size), mode="bilinear", antialias=True, align_corners=False)
+        out.append(c.flip(3) if row[3] < 0 else c)
+    return torch.cat(out)
+
+
+def augment_reference_ragged(data: torch.Tensor, meta: torch.Tensor, params: torch.Tensor, size: int, rad: int,
+                             mean, std) -> torch.Tensor:
+    """Tensor-op implementation of ``dedloc::multicrop_ragged``: [nb, 3, size, size] bf16, channels-last."""
+    if params.shape[0] == 0:
+        return torch.empty(0, 3, size, size, dtype=torch.bfloat16, device=data.device).contiguous(
+            memory_format=torch.channels_last)
+    return _color_blur_norm(crop_resize_ragged(data, meta, params, size), params.float(), size, rad, mean, std)
+
+
 class MultiCropAugment:
     def __init__(self, size_crops: Sequence[int] = (224, 96), num_crops: Sequence[int] = (2, 6),
                  crop_scales: Sequence[Tuple[float, float]] = ((0.14, 1.0), (0.05, 0.14)),
@@ -94,13 +135,10 @@ class MultiCropAugment:
 
     def sample_params(self, src: torch.Tensor, scale, gen: torch.Generator) -> torch.Tensor:
         """Host-side draws for one crop resolution: [nb, 20] fp32 table (layout: augment.hip)."""
-        nb, s = src.shape[0], self.s
+        nb = src.shape[0]
 
         def u(lo, hi):
             return torch.empty(nb, dtype=torch.float64).uniform_(lo, hi, generator=gen)
-
-        def coin(p):
-            return torch.rand(nb, dtype=torch.float64, generator=gen) < p
 
         # RandomResizedCrop(scale, ratio 3/4..4/3) + horizontal flip, normalized coordinates
         area = u(scale[0], scale[1])
@@ -109,6 +147,20 @@ class MultiCropAugment:
         h = torch.sqrt(area / r).clamp(max=1.0)
         cx = (torch.rand(nb, dtype=torch.float64, generator=gen) * (1 - w) + w / 2) * 2 - 1
         cy = (torch.rand(nb, dtype=torch.float64, generator=gen) * (1 - h) + h / 2) * 2 - 1
+        flip, tail = self._draw_flip_color_blur(nb, gen)
+        return torch.cat([torch.stack([src.double(), w * flip, cx, h, cy], 1), tail], 1).float()
+
+    def _draw_flip_color_blur(self, nb: int, gen: torch.Generator):
+        """The draws after the geometry, shared by both sources: flip sign [nb] and table columns
+        5-19 [nb, 15] (float64)."""
+        s = self.s
+
+        def u(lo, hi):
+            return torch.empty(nb, dtype=torch.float64).uniform_(lo, hi, generator=gen)
+
+        def coin(p):
+            return torch.rand(nb, dtype=torch.float64, generator=gen) < p
+
         flip = torch.where(coin(self.flip_p), -1.0, 1.0).double()
         lo, hi = max(0.0, 1 - 0.8 * s), 1 + 0.8 * s
         bright, contrast, sat = u(lo, hi), u(lo, hi), u(lo, hi)
@@ -121,8 +173,58 @@ class MultiCropAugment:
         rot[:, 0, 0] = 1
         rot[:, 1, 1], rot[:, 1, 2], rot[:, 2, 1], rot[:, 2, 2] = hue.cos(), -hue.sin(), hue.sin(), hue.cos()
         M = torch.linalg.inv(_YIQ) @ rot @ _YIQ
-        t = torch.stack([src.double(), w * flip, cx, h, cy, bright, contrast, sat, apply, grey], 1)
-        return torch.cat([t, M.reshape(nb, 9), sigma.view(-1, 1)], 1).float()
+        t = torch.stack([bright, contrast, sat, apply, grey], 1)
+        return flip, torch.cat([t, M.reshape(nb, 9), sigma.view(-1, 1)], 1)
+
+    def sample_params_ragged(self, src: torch.Tensor, H: torch.Tensor, W: torch.Tensor, scale,
+                             gen: torch.Generator) -> torch.Tensor:
+        """Host-side draws for one crop resolution over images of different sizes ([nb] rows ``src``
+        of the batch's image table, their heights ``H`` and widths ``W``): [nb, 20] fp32 table for
+        ``dedloc::multicrop_ragged`` (columns 0-4: row, box left, top, width (negative: mirrored),
+        height, in pixels).  The box is torchvision's ``RandomResizedCrop.get_params``, vectorised:
+        ten attempts, the first that fits wins, else the centred box with its ratio clamped."""
+        nb = src.shape[0]
+        Hd, Wd = H.double(), W.double()
+        tries = 10
+        area = torch.empty(nb, tries, dtype=torch.float64).uniform_(scale[0], scale[1], generator=gen) * (Hd * Wd)[:, None]
+        r = torch.exp(torch.empty(nb, tries, dtype=torch.float64).uniform_(math.log(3 / 4), math.log(4 / 3),
+                                                                           generator=gen))
+        w = torch.round(torch.sqrt(area * r))
+        h = torch.round(torch.sqrt(area / r))
+        ok = (w > 0) & (w <= Wd[:, None]) & (h > 0) & (h <= Hd[:, None])
+        first = ok.double().argmax(1, keepdim=True)  # the first fitting attempt (0 when none fits)
+        w, h, fits = w.gather(1, first)[:, 0], h.gather(1, first)[:, 0], ok.any(1)
+        # fallback: the whole image, cut to the nearest ratio in [3/4, 4/3], centred
+        ratio = Wd / Hd
+        fw = torch.where(ratio > 4 / 3, torch.round(Hd * (4 / 3)), Wd)
+        fh = torch.where(ratio < 3 / 4, torch.round(Wd / (3 / 4)), Hd)
+        ui, uj = (torch.rand(nb, dtype=torch.float64, generator=gen) for _ in range(2))
+        w, h = torch.where(fits, w, fw), torch.where(fits, h, fh)
+        i = torch.where(fits, torch.floor(ui * (Hd - h + 1)).clamp(max=Hd - h), torch.floor((Hd - h) / 2))
+        j = torch.where(fits, torch.floor(uj * (Wd - w + 1)).clamp(max=Wd - w), torch.floor((Wd - w) / 2))
+        flip, tail = self._draw_flip_color_blur(nb, gen)
+        return torch.cat([torch.stack([src.double(), j, i, w * flip, h], 1), tail], 1).float()
+
+    @torch.no_grad()
+    def ragged(self, data: torch.Tensor, meta: torch.Tensor, H: torch.Tensor, W: torch.Tensor, gen: torch.Generator,
+               out_dtype=torch.bfloat16) -> List[torch.Tensor]:
+        """Multi-crop of a ragged uint8 batch (``data`` / ``meta`` on the device, layout in
+        augment.hip; ``H``, ``W``: the same sizes on the host): one [b, 3, s, s] channels-last tensor
+        per crop."""
+        import dedloc_amd.ops  # noqa: F401  (registers dedloc::multicrop_ragged)
+
+        b = meta.shape[0]
+        src = torch.arange(b)
+        crops = []
+        for size, n, scale in zip(self.size_crops, self.num_crops, self.crop_scales):
+            params = self.sample_params_ragged(src.repeat(n), H.repeat(n), W.repeat(n), scale, gen)
+            if data.is_cuda:
+                params = params.pin_memory().to(data.device, non_blocking=True)
+            x = torch.ops.dedloc.multicrop_ragged(data, meta, params, size, self.rad, list(self.mean), list(self.std))
+            if x.dtype != out_dtype:
+                x = x.to(out_dtype)
+            crops.extend(x.split(b))
+        return crops
 
     @torch.no_grad()
     def __call__(self, pool: torch.Tensor, src: torch.Tensor, gen: torch.Generator,

@@ -71,6 +71,7 @@ _SCHEMAS = [
     "l2norm_fwd(Tensor x, float eps) -> (Tensor, Tensor)",
     "l2norm_bwd(Tensor dy, Tensor y, Tensor rinv) -> Tensor",
     "multicrop(Tensor pool, Tensor params, int size, int rad, float[] mean, float[] std) -> Tensor",
+    "multicrop_ragged(Tensor bytes, Tensor meta, Tensor params, int size, int rad, float[] mean, float[] std) -> Tensor",
     "bn_fwd(Tensor x, Tensor? res, Tensor gamma, Tensor beta, Tensor(a!)? running_mean, Tensor(b!)? running_var, "
     "float eps, float momentum, bool relu, int groups=1, Tensor(c!)? sums=None, bool stats_ready=False) "
     "-> (Tensor, Tensor, Tensor)",
@@ -795,6 +796,13 @@ def _multicrop_cpu(pool, params, size, rad, mean, std):
     from dedloc_amd.data.multicrop import augment_reference
 
     return augment_reference(pool, params, size, rad, mean, std)
+
+
+@_impl("multicrop_ragged")
+def _multicrop_ragged_cpu(bytes, meta, params, size, rad, mean, std):
+    from dedloc_amd.data.multicrop import augment_reference_ragged
+
+    return augment_reference_ragged(bytes, meta, params, size, rad, mean, std)
 
 
 @_impl("bmm")

@@ -71,6 +71,12 @@ class SwavPeer:
         mcfg, lcfg, ocfg = cfg.MODEL, cfg.LOSS.swav_loss, cfg.OPTIMIZER
         dcfg = cfg.DATA.TRAIN
         self.batch_size = int(dcfg.BATCHSIZE_PER_REPLICA)
+        sources = dcfg.get("DATA_SOURCES") or ["synthetic"]
+        source = sources if isinstance(sources, str) else sources[0]
+        if source not in ("synthetic", "disk_folder"):  # before anything is started
+            raise ValueError(f"DATA.TRAIN.DATA_SOURCES={sources!r}: the sources are 'synthetic' and 'disk_folder'")
+        if source == "disk_folder" and not dcfg.get("DATA_PATHS"):
+            raise ValueError("DATA.TRAIN.DATA_SOURCES=[disk_folder] needs DATA.TRAIN.DATA_PATHS=[directory, ...]")
         if impl == "eager":
             from .swav_eager import EagerSwAVModel
 
@@ -156,10 +162,21 @@ class SwavPeer:
                                color_strength=float(mc.color_strength), blur_p=float(mc.blur_p),
                                blur_radius=tuple(mc.blur_radius))
         seed = int.from_bytes(self.local_public_key[-8:], "little") ^ int(cfg.get("SEED_VALUE", 0))
-        self.data = SyntheticMultiCropStream(self.batch_size, self.device, seed=seed,
-                                             pool_size=int(dcfg.get("SYNTHETIC_POOL_SIZE", 1024)),
-                                             image_size=int(dcfg.get("SYNTHETIC_IMAGE_SIZE", 256)), augment=aug,
-                                             out_dtype=torch.bfloat16 if self.device.type == "cuda" else torch.float32)
+        out_dtype = torch.bfloat16 if self.device.type == "cuda" else torch.float32
+        if source == "synthetic":
+            self.data = SyntheticMultiCropStream(self.batch_size, self.device, seed=seed,
+                                                 pool_size=int(dcfg.get("SYNTHETIC_POOL_SIZE", 1024)),
+                                                 image_size=int(dcfg.get("SYNTHETIC_IMAGE_SIZE", 256)), augment=aug,
+                                                 out_dtype=out_dtype)
+        else:  # disk_folder, vissl's source of the reference run; DATASET_NAMES is accepted and ignored
+            from ..data.image_folder import ImageFolderDataset, ImageFolderMultiCropStream
+
+            paths = dcfg.DATA_PATHS
+            dataset = ImageFolderDataset([paths] if isinstance(paths, str) else list(paths),
+                                         max_image_side=int(dcfg.get("MAX_IMAGE_SIDE", 512)))
+            self.data = ImageFolderMultiCropStream(self.batch_size, self.device, dataset, seed=seed, augment=aug,
+                                                   out_dtype=out_dtype,
+                                                   num_workers=int(dcfg.get("NUM_DATALOADER_WORKERS", 8)))
         if self.device.type == "cuda" and bool(dcfg.get("PREFETCH", True)):
             self.data = StreamPrefetcher(self.data, self.device)  # next batch's crops under this step's compute
         self.frozen = [(name, int(iters)) for name, iters in (mcfg.get("TEMP_FROZEN_PARAMS_ITER_MAP") or [])]
@@ -418,5 +435,7 @@ class SwavPeer:
                 break
 
     def shutdown(self):
+        if hasattr(self.data, "close"):  # disk_folder: the decode threads
+            self.data.close()
         self.collab_opt.shutdown()
         self.dht.shutdown()
