@@ -598,13 +598,14 @@ std::tuple<at::Tensor, at::Tensor> attn_softmax_bwd(const at::Tensor& s, const a
 // There is no vendor-library or ATen path: a shape no kernel takes is an error, not a fallback.
 // The fp32-accumulating weight-gradient form writes straight into the fp32 gradient buffer, so the
 // shared ALBERT layer's 24 weight-gradient contributions never round through bf16.
-constexpr bool use_gemm8() { return true; }
+// Every call is one DlGemm descriptor (dl_kernels.h) handed to gemm_route below, the only place
+// that calls the three launchers; docs/KERNELS.md "GEMM dispatch" has the rules per call site.
 
 // Which kernel took each GEMM of this section: process-wide launch counts, bumped where a launcher
 // returned 0 (host side only: no effect on dispatch, no synchronisation).  The tests read them
 // before and after a call (`dedloc_ws::gemm_backend_counts()`), so a contract check that turns too
 // strict and silently moves a shape to a slower kernel fails a test.
-enum { kGemm8 = 0, kGemmTiled = 1, kGemmSmall = 2 };
+enum { kGemmNone = -1, kGemm8 = 0, kGemmTiled = 1, kGemmSmall = 2 };
 std::atomic<int64_t> g_gemm_backend[3];
 
 inline int took(int backend, int rc) {
@@ -614,23 +615,6 @@ inline int took(int backend, int rc) {
 
 std::vector<int64_t> gemm_backend_counts() {  // {gemm8.hip, gemm.hip, gemm_small.hip}
   return {g_gemm_backend[kGemm8].load(), g_gemm_backend[kGemmTiled].load(), g_gemm_backend[kGemmSmall].load()};
-}
-
-struct Mat {  // (rows, k) operand view: K-inner means element (r, k) at p[r*ld + k]
-  const at::Tensor& t;
-  bool kouter;
-  int64_t rows, k, ld;
-  long srow() const { return kouter ? 1 : (long)ld; }
-  long sk() const { return kouter ? (long)ld : 1; }
-};
-
-// op(a) is [M, K]; trans_a=False -> a is [M,K] K-inner; trans_a=True -> a is [K,M] (K-outer)
-inline Mat a_view(const at::Tensor& a, bool trans_a) {
-  return trans_a ? Mat{a, true, a.size(1), a.size(0), a.stride(0)} : Mat{a, false, a.size(0), a.size(1), a.stride(0)};
-}
-// op(b) is [K, N]; trans_b=True -> b is [N,K] (K-inner); trans_b=False -> b is [K,N] (K-outer)
-inline Mat b_view(const at::Tensor& b, bool trans_b) {
-  return trans_b ? Mat{b, false, b.size(0), b.size(1), b.stride(0)} : Mat{b, true, b.size(1), b.size(0), b.stride(0)};
 }
 
 inline void expect_operands(const at::Tensor& a, const at::Tensor& b) {
@@ -646,64 +630,61 @@ inline at::Tensor f32_bias(const c10::optional<at::Tensor>& bias, int64_t n) {
   return bias->scalar_type() == at::kFloat ? bias->contiguous() : bias->to(at::kFloat).contiguous();
 }
 
-// The tiled kernels: gemm8.hip where its contract holds, gemm.hip otherwise.  0 on success.
-int own_gemm(int akout, int bkout, int epi, const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N, int K,
-             bf16_t* C, long ldc, float* Cf, long ldcf, const float* bias, const bf16_t* R, long ldr, bf16_t* H,
-             long ldh, float* dbias, hipStream_t st) {
-  if (use_gemm8() && took(kGemm8, dl_gemm8(akout, bkout, epi, A, lda, B, ldb, M, N, K, C, ldc, Cf, ldcf, 0,
-                                           epi == 3 ? 1 : 0, bias, R, ldr, H, ldh, dbias, 1, st)) == 0)
-    return 0;
-  return took(kGemmTiled,
-              dl_gemm(akout, bkout, epi, A, lda, B, ldb, M, N, K, C, ldc, Cf, ldcf, bias, R, ldr, H, ldh, dbias, 1, st));
+// The operands and extents of op(a) op(b) with its bf16 output; the caller names the epilogue and
+// that epilogue's fields.  op(a) is [M, K]: a itself, or with trans_a its transpose (a is [K, M], a
+// K-outer operand).  op(b) is [K, N]: with trans_b b is [N, K] (K-inner), else [K, N] (K-outer).
+inline DlGemm gemm_desc(const at::Tensor& a, bool trans_a, const at::Tensor& b, bool trans_b, bf16_t* C = nullptr,
+                        long ldc = 0) {
+  DlGemm g;
+  g.A = cbf(a), g.lda = a.stride(0), g.a_kouter = trans_a;
+  g.B = cbf(b), g.ldb = b.stride(0), g.b_kouter = !trans_b;
+  g.M = (int)a.size(trans_a ? 1 : 0), g.N = (int)b.size(trans_b ? 0 : 1), g.K = (int)a.size(trans_a ? 0 : 1);
+  TORCH_CHECK(b.size(trans_b ? 1 : 0) == g.K, "gemm inner dimensions differ");
+  g.C = C, g.ldc = ldc;
+  return g;
 }
 
-// gemm_small with its reduction split chosen for the shape (fp32 slab workspace from the caching
-// allocator when split)
-void small_gemm(int epi, const Mat& A, const Mat& B, const at::Tensor& a, const at::Tensor& b, bf16_t* C, long ldc,
-                float* Cf, long ldcf, int accumulate, const float* bias, const bf16_t* R, long ldr, hipStream_t st) {
-  const int M = (int)A.rows, N = (int)B.rows, K = (int)A.k;
-  const int S = dl_gemm_small_splits(M, N, K);
+// The one place a GEMM kernel is chosen.  Tries the kernels `allow` permits in the fixed order
+// gemm8 -> gemm.hip -> gemm_small, each with the descriptor as the caller filled it, and returns the
+// one that took the call (counted) or kGemmNone.  gemm_small's reduction split is its own
+// (dl_gemm_small_splits, replacing g.splits), with the fp32 slab workspace from the caching
+// allocator on `like`'s device when it splits; its split form has no statistics epilogue, so a
+// descriptor with `stats` is refused there before anything is allocated.
+enum : unsigned { kUse8 = 1, kUseTiled = 2, kUseSmall = 4 };
+int gemm_route(const DlGemm& g, unsigned allow, const at::Tensor& like, hipStream_t st) {
+  if ((allow & kUse8) && took(kGemm8, dl_gemm8(g, st)) == 0) return kGemm8;
+  if ((allow & kUseTiled) && took(kGemmTiled, dl_gemm(g, st)) == 0) return kGemmTiled;
+  if (!(allow & kUseSmall)) return kGemmNone;
+  DlGemm s = g;
+  s.splits = dl_gemm_small_splits(g.M, g.N, g.K);
+  if (s.splits > 1 && g.stats) return kGemmNone;
   at::Tensor ws;
-  if (S > 1) ws = at::empty({(int64_t)S * M * N}, a.options().dtype(at::kFloat));
-  check(took(kGemmSmall, dl_gemm_small(epi, cbf(a), A.srow(), A.sk(), cbf(b), B.srow(), B.sk(), M, N, K, C, ldc, Cf,
-                                       ldcf, accumulate, bias, R, ldr, S, S > 1 ? f32(ws) : nullptr, st)),
-        "gemm_small");
+  if (s.splits > 1) ws = at::empty({(int64_t)s.splits * g.M * g.N}, like.options().dtype(at::kFloat));
+  return took(kGemmSmall, dl_gemm_small(s, s.splits > 1 ? f32(ws) : nullptr, st)) == 0 ? kGemmSmall : kGemmNone;
 }
 
 // C (bf16) = op(A) op(B) (+ bias) (+ R): gemm8 where its contract holds; outputs of at most 192
 // columns (1x1 convs with 64 / 128 channels, the stem, ALBERT's 128-wide embedding side) on
 // gemm_small's 128x64 / 128x128 tiles (a 256-wide tile would waste half to three quarters of its
 // MFMAs); the register-staged 256x256 gemm.hip for the remaining wide shapes; gemm_small last.
-void gemm_store(const Mat& A, const Mat& B, const at::Tensor& a, const at::Tensor& b, bf16_t* C, long ldc,
-                const float* bias, const bf16_t* R, long ldr, hipStream_t st) {
-  if (use_gemm8() &&
-      took(kGemm8, dl_gemm8(A.kouter, B.kouter, 0, cbf(a), A.ld, cbf(b), B.ld, (int)A.rows, (int)B.rows, (int)A.k, C,
-                            ldc, nullptr, 0, 0, 0, bias, R, ldr, nullptr, 0, nullptr, 1, st)) == 0)
-    return;
-  if (B.rows > 192 &&
-      took(kGemmTiled, dl_gemm(A.kouter, B.kouter, 0, cbf(a), A.ld, cbf(b), B.ld, (int)A.rows, (int)B.rows, (int)A.k,
-                               C, ldc, nullptr, 0, bias, R, ldr, nullptr, 0, nullptr, 1, st)) == 0)
-    return;
-  small_gemm(0, A, B, a, b, C, ldc, nullptr, 0, 0, bias, R, ldr, st);
+void gemm_store(const DlGemm& g, const at::Tensor& like, hipStream_t st) {
+  TORCH_CHECK(gemm_route(g, kUse8 | (g.N > 192 ? kUseTiled : 0) | kUseSmall, like, st) != kGemmNone,
+              "dedloc_amd: unsupported shape for gemm");
 }
 
 // gemm_store plus the BatchNorm statistics of the stored values (stats [M / stat_rows][2N], fp32,
-// accumulated): in the GEMM epilogue where the kernel takes it (gemm8 EPI 4 for N % 256 == 0,
-// gemm_small for the narrow outputs), else one statistics pass over C afterwards
-void gemm_store_stats(const Mat& A, const Mat& B, const at::Tensor& a, const at::Tensor& b, bf16_t* C, long ldc,
-                      float* stats, long stat_rows, hipStream_t st) {
-  const int M = (int)A.rows, N = (int)B.rows, K = (int)A.k;
-  if (use_gemm8() &&
-      took(kGemm8, dl_gemm8(A.kouter, B.kouter, 4, cbf(a), A.ld, cbf(b), B.ld, M, N, K, C, ldc, nullptr, 0, 0, 0,
-                            nullptr, nullptr, 0, nullptr, 0, nullptr, 1, st, stats, stat_rows)) == 0)
-    return;
-  if (N <= 192 && dl_gemm_small_splits(M, N, K) == 1 &&
-      took(kGemmSmall, dl_gemm_small(0, cbf(a), A.srow(), A.sk(), cbf(b), B.srow(), B.sk(), M, N, K, C, ldc, nullptr,
-                                     0, 0, nullptr, nullptr, 0, 1, nullptr, st, stats, stat_rows)) == 0)
-    return;
-  gemm_store(A, B, a, b, C, ldc, nullptr, nullptr, 0, st);
-  TORCH_CHECK(ldc == N, "gemm_store_stats: the statistics pass needs a dense C");
-  check(dl_bn_stats(C, stats, stat_rows, N, (int)(M / stat_rows), st), "bn_stats");
+// accumulated): in the GEMM epilogue where the kernel takes it (gemm8's STATS for N % 256 == 0,
+// gemm_small's unsplit store for the narrow outputs), else one statistics pass over C afterwards
+void gemm_store_stats(DlGemm g, float* stats, long stat_rows, const at::Tensor& like, hipStream_t st) {
+  g.stats = stats, g.stat_rows = stat_rows;
+  g.epi = DL_EPI_STATS;
+  if (gemm_route(g, kUse8, like, st) != kGemmNone) return;
+  g.epi = DL_EPI_STORE;
+  if (g.N <= 192 && gemm_route(g, kUseSmall, like, st) != kGemmNone) return;
+  g.stats = nullptr;
+  gemm_store(g, like, st);
+  TORCH_CHECK(g.ldc == g.N, "gemm_store_stats: the statistics pass needs a dense C");
+  check(dl_bn_stats(g.C, stats, stat_rows, g.N, (int)(g.M / stat_rows), st), "bn_stats");
 }
 
 // out[b] = a[b] @ b[b] (torch.bmm semantics; any element strides, e.g. transposed views, read in
@@ -728,24 +709,24 @@ at::Tensor bmm(const at::Tensor& a, const at::Tensor& b, bool out_f32) {
 at::Tensor gemm(const at::Tensor& a, const at::Tensor& b, const c10::optional<at::Tensor>& bias,
                 const c10::optional<at::Tensor>& residual, bool trans_a, bool trans_b, int64_t epilogue) {
   expect_operands(a, b);
-  const Mat A = a_view(a, trans_a), B = b_view(b, trans_b);
-  TORCH_CHECK(A.k == B.k, "gemm inner dimensions differ");
+  DlGemm g = gemm_desc(a, trans_a, b, trans_b);
   if (residual.has_value()) {
     TORCH_CHECK(residual->scalar_type() == at::kBFloat16 && residual->is_contiguous() &&
-                    residual->size(0) == A.rows && residual->size(1) == B.rows,
+                    residual->size(0) == g.M && residual->size(1) == g.N,
                 "gemm residual must be a contiguous bf16 [M, N] tensor");
   }
-  auto c = at::empty({A.rows, B.rows}, a.options());
-  const at::Tensor bias32 = f32_bias(bias, B.rows);
-  const float* bp = bias32.defined() ? f32(bias32) : nullptr;
-  const bf16_t* rp = residual.has_value() ? cbf(*residual) : nullptr;
-  gemm_store(A, B, a, b, bf(c), B.rows, bp, rp, B.rows, cur_stream(a));
+  auto c = at::empty({g.M, g.N}, a.options());
+  const at::Tensor bias32 = f32_bias(bias, g.N);
+  g.C = bf(c), g.ldc = g.N;
+  if (bias32.defined()) g.bias = f32(bias32);
+  if (residual.has_value()) g.R = cbf(*residual), g.ldr = g.N;
+  gemm_store(g, a, cur_stream(a));
   if (epilogue == 1) check(dl_gelu_fwd(cbf(c), bf(c), c.numel(), cur_stream(c)), "gemm gelu epilogue");
   return c;
 }
 
 // fp32-accumulating weight gradient c += op(a) op(b) through gemm8: the token (reduction) dimension
-// is split into S slices written as fp32 slabs and summed into c (no atomics); -1 if unsupported.
+// is split into S slices written as fp32 slabs and summed into c (no atomics).
 // Weight gradients have few output tiles (48 for ALBERT's QKV) and a very long reduction (the
 // tokens), so the reduction is split into S slices; S is chosen for whole waves of workgroups on
 // the 256 CUs (one gemm8 workgroup per CU): 48 tiles x 8 slices = 384 workgroups would leave half
@@ -755,14 +736,14 @@ at::Tensor gemm(const at::Tensor& a, const at::Tensor& b, const c10::optional<at
 #ifndef DL_WGRAD_CUS
 #define DL_WGRAD_CUS 256  // CUs one weight gradient is split to fill (a measurement build may override)
 #endif
-int wgrad_splits8(const Mat& A, const Mat& B) {
-  const int64_t tiles = ((A.rows + 255) / 256) * ((B.rows + 255) / 256);
-  // any S dividing the K-tile count (SwAV's 14x14 maps: 25088 tokens = 392 K-tiles = 2^3 7^2, so
-  // S = 56 puts 224 workgroups on the chip where powers of two stop at 32), each slice at least 4
-  // K-tiles (8 while S > 32)
+int wgrad_splits8(int64_t M, int64_t N, int64_t K) {
+  const int64_t tiles = ((M + 255) / 256) * ((N + 255) / 256);
+  // any S dividing the K-tile count, each slice at least 4 K-tiles (8 while S > 32).  SwAV's 14x14
+  // maps: 25088 tokens = 392 K-tiles = 2^3 7^2 with one output tile get S = 49 (49 workgroups of 8
+  // K-tiles, where powers of two stop at 32); S = 56 would leave 7 K-tiles per slice, below the floor
   constexpr int64_t kCUs = DL_WGRAD_CUS;
-  const int64_t ktiles = A.k / 64;
-  if (A.k % 64) return 1;
+  const int64_t ktiles = K / 64;
+  if (K % 64) return 1;
   int best = 1;
   double best_eff = 0.0;
   for (int S = 1; S <= 64; ++S) {
@@ -778,37 +759,40 @@ int wgrad_splits8(const Mat& A, const Mat& B) {
   return best;
 }
 
-int own_wgrad(const Mat& A, const Mat& B, const at::Tensor& a, const at::Tensor& b, at::Tensor c, hipStream_t st) {
-  if (!use_gemm8() || !c.is_contiguous()) return -1;
-  const int S = wgrad_splits8(A, B);
-  if (S == 1)
-    return took(kGemm8, dl_gemm8(A.kouter, B.kouter, 3, cbf(a), A.ld, cbf(b), B.ld, (int)A.rows, (int)B.rows,
-                                 (int)A.k, nullptr, 0, f32(c), c.stride(0), 0, 1, nullptr, nullptr, 0, nullptr, 0,
-                                 nullptr, 1, st));
-  auto slabs = at::empty({S, A.rows, B.rows}, c.options());
-  const int rc = took(kGemm8, dl_gemm8(A.kouter, B.kouter, 3, cbf(a), A.ld, cbf(b), B.ld, (int)A.rows, (int)B.rows,
-                                       (int)A.k, nullptr, 0, f32(slabs), B.rows, A.rows * B.rows, 0, nullptr, nullptr,
-                                       0, nullptr, 0, nullptr, S, st));
-  if (rc != 0) return rc;
-  return dl_sum_slabs(f32(c), f32(slabs), S, (size_t)c.numel(), st);
+// the split count gemm8's weight gradient c [M, N] += over K tokens takes (host arithmetic only)
+int64_t gemm_wgrad_splits(int64_t M, int64_t N, int64_t K) { return wgrad_splits8(M, N, K); }
+
+// gemm8's weight-gradient form: reduction slice z of S writes (accumulate: adds to) slab z of the
+// dense fp32 [S, M, N] at `out`.  False when gemm8 refuses the shape.
+bool wgrad8(DlGemm g, float* out, int S, bool accumulate, const at::Tensor& like, hipStream_t st) {
+  g.epi = DL_EPI_F32;
+  g.Cf = out, g.ldcf = g.N, g.slab = S > 1 ? (long)g.M * g.N : 0, g.accumulate = accumulate;
+  g.splits = S;
+  return gemm_route(g, kUse8, like, st) == kGemm8;
 }
 
 void gemm_acc_f32(const at::Tensor& a, const at::Tensor& b, at::Tensor c, bool trans_a, bool trans_b) {
   expect_operands(a, b);
   TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat && c.dim() == 2 && c.stride(1) == 1,
               "gemm_acc_f32: c must be an fp32 [M, N] GPU tensor with unit inner stride");
-  const Mat A = a_view(a, trans_a), B = b_view(b, trans_b);
-  TORCH_CHECK(A.k == B.k, "gemm inner dimensions differ");
-  TORCH_CHECK(c.size(0) == A.rows && c.size(1) == B.rows, "gemm_acc_f32: c shape mismatch");
-  if (own_wgrad(A, B, a, b, c, cur_stream(a)) == 0) return;
-  // gemm.hip: split the long reduction over ~2 workgroups per CU, fp32 atomics into c
-  const int64_t tiles = ((A.rows + 255) / 256) * ((B.rows + 255) / 256);
-  const int splits = (int)std::max<int64_t>(1, std::min<int64_t>(A.k / 1024, (512 + tiles - 1) / tiles));
-  if (took(kGemmTiled, dl_gemm(A.kouter, B.kouter, 3, cbf(a), A.ld, cbf(b), B.ld, (int)A.rows, (int)B.rows, (int)A.k,
-                               nullptr, 0, f32(c), c.stride(0), nullptr, nullptr, 0, nullptr, 0, nullptr, splits,
-                               cur_stream(a))) == 0)
-    return;
-  small_gemm(1, A, B, a, b, nullptr, 0, f32(c), c.stride(0), 1, nullptr, nullptr, 0, cur_stream(a));
+  DlGemm g = gemm_desc(a, trans_a, b, trans_b);
+  TORCH_CHECK(c.size(0) == g.M && c.size(1) == g.N, "gemm_acc_f32: c shape mismatch");
+  const hipStream_t st = cur_stream(a);
+  if (c.is_contiguous()) {  // gemm8 writes dense slabs: c itself when it does not split
+    const int S = wgrad_splits8(g.M, g.N, g.K);
+    const at::Tensor slabs = S > 1 ? at::empty({S, g.M, g.N}, c.options()) : c;
+    if (wgrad8(g, f32(slabs), S, S == 1, a, st)) {
+      if (S > 1) check(dl_sum_slabs(f32(c), f32(slabs), S, (size_t)c.numel(), st), "sum_slabs");
+      return;
+    }
+  }
+  // gemm.hip: split the long reduction over ~2 workgroups per CU, fp32 atomics into c; gemm_small last
+  const int64_t tiles = ((g.M + 255) / 256) * ((g.N + 255) / 256);
+  g.epi = DL_EPI_F32;
+  g.Cf = f32(c), g.ldcf = c.stride(0), g.accumulate = 1;
+  g.splits = (int)std::max<int64_t>(1, std::min<int64_t>(g.K / 1024, (512 + tiles - 1) / tiles));
+  TORCH_CHECK(gemm_route(g, kUseTiled | kUseSmall, a, st) != kGemmNone,
+              "dedloc_amd: unsupported shape for gemm_acc_f32");
 }
 
 // Weight gradient of a weight that several consecutive backward calls share (ALBERT's one layer,
@@ -869,18 +853,15 @@ void gemm_acc_f32_shared(const at::Tensor& a, const at::Tensor& b, at::Tensor c,
                          bool first, bool last) {
   expect_operands(a, b);
   TORCH_CHECK(c.is_cuda() && c.scalar_type() == at::kFloat, "gemm_acc_f32_shared: c must be fp32");
-  const Mat A = a_view(a, trans_a), B = b_view(b, trans_b);
-  TORCH_CHECK(A.k == B.k && c.size(0) == A.rows && c.size(1) == B.rows, "gemm_acc_f32_shared: shape mismatch");
-  const int S = use_gemm8() && c.is_contiguous() ? wgrad_splits8(A, B) : 1;
+  const DlGemm g = gemm_desc(a, trans_a, b, trans_b);
+  TORCH_CHECK(c.size(0) == g.M && c.size(1) == g.N, "gemm_acc_f32_shared: shape mismatch");
+  const int S = c.is_contiguous() ? wgrad_splits8(g.M, g.N, g.K) : 1;
   if (S > 1) {
     SlabSet& set = shared_slabs(c, S);
     if (first) set.live = false;
     // a shape gemm8 refuses (small heads, odd widths) falls through to the direct fp32 accumulation;
     // slabs that hold this series' earlier partial sums are still added by the last call
-    const int rc = took(kGemm8, dl_gemm8(A.kouter, B.kouter, 3, cbf(a), A.ld, cbf(b), B.ld, (int)A.rows, (int)B.rows,
-                                         (int)A.k, nullptr, 0, f32(set.slabs), B.rows, A.rows * B.rows,
-                                         set.live ? 1 : 0, nullptr, nullptr, 0, nullptr, 0, nullptr, S, cur_stream(a)));
-    if (rc == 0) set.live = true;
+    if (wgrad8(g, f32(set.slabs), S, set.live, a, cur_stream(a))) set.live = true;
     else gemm_acc_f32(a, b, c, trans_a, trans_b);
     if (last && set.live) {
       check(dl_sum_slabs(f32(c), f32(set.slabs), S, (size_t)c.numel(), cur_stream(a)), "sum_slabs");
@@ -891,89 +872,73 @@ void gemm_acc_f32_shared(const at::Tensor& a, const at::Tensor& b, at::Tensor c,
   gemm_acc_f32(a, b, c, trans_a, trans_b);
 }
 
-// fused FFN-up: H = x W^T + b (pre-activation, kept for backward), G = gelu_new(H).  trans_w: w
-// holds W^T ([in, out]: a K-outer B operand) instead of W ([out, in], K-inner)
-std::tuple<at::Tensor, at::Tensor> gemm_gelu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& bias,
-                                             bool trans_w) {
+// fused FFN-up: h = bf16(x W^T + b), G = gelu_new(h), and for the backward either h itself
+// (gemm_gelu) or, with `deriv`, D = gelu_new'(h) (gemm_gelu_d, gemm8 only: the backward then
+// multiplies by D instead of evaluating gelu_new' — gemm_dmul).  trans_w: w holds W^T ([in, out]: a
+// K-outer B operand) instead of W ([out, in], K-inner).  Returns (h or D, G).
+std::tuple<at::Tensor, at::Tensor> ffn_up(const at::Tensor& x, const at::Tensor& w, const at::Tensor& bias,
+                                          bool trans_w, bool deriv) {
   expect_operands(x, w);
   const int64_t nout = trans_w ? w.size(1) : w.size(0);
   auto H = at::empty({x.size(0), nout}, x.options());
   auto G = at::empty_like(H);
   const at::Tensor bias32 = f32_bias(bias, nout);
-  if (own_gemm(0, trans_w ? 1 : 0, 1, cbf(x), x.stride(0), cbf(w), w.stride(0), (int)x.size(0), (int)nout,
-               (int)x.size(1), bf(G), G.size(1), nullptr, 0, f32(bias32), nullptr, 0, bf(H), H.size(1), nullptr,
-               cur_stream(x)) == 0)
-    return {H, G};
-  const Mat A = a_view(x, false), B = b_view(w, !trans_w);
-  gemm_store(A, B, x, w, bf(H), H.size(1), f32(bias32), nullptr, 0, cur_stream(x));
-  check(dl_gelu_fwd(cbf(H), bf(G), H.numel(), cur_stream(H)), "gelu_fwd");
+  const hipStream_t st = cur_stream(x);
+  DlGemm g = gemm_desc(x, false, w, !trans_w, bf(G), nout);
+  g.epi = deriv ? DL_EPI_GELUD : DL_EPI_GELU;
+  g.bias = f32(bias32);
+  g.H = bf(H), g.ldh = nout;
+  if (gemm_route(g, deriv ? kUse8 : kUse8 | kUseTiled, x, st) != kGemmNone) return {H, G};
+  const at::Tensor pre = deriv ? at::empty_like(H) : H;  // unfused: the plain store, then the elementwise kernel
+  g.epi = DL_EPI_STORE;
+  g.C = bf(pre), g.H = nullptr;
+  gemm_store(g, x, st);
+  if (deriv) check(dl_gelu_fwd_d(cbf(pre), bf(G), bf(H), pre.numel(), st), "gelu_fwd_d");
+  else check(dl_gelu_fwd(cbf(pre), bf(G), pre.numel(), st), "gelu_fwd");
   return {H, G};
 }
-
-// fused FFN dgrad: C = (dy W) * gelu_new'(F), dbias += colsum(C).  trans_w: w holds W^T (the
-// forward-layout copy, a K-inner operand for the tiled kernels)
-at::Tensor gemm_dgelu(const at::Tensor& dy, const at::Tensor& w, const at::Tensor& F, at::Tensor dbias,
-                      bool trans_w) {
-  expect_operands(dy, w);
-  expect(F, at::kBFloat16, "F");
-  expect(dbias, at::kFloat, "dbias");
-  const int64_t nout = trans_w ? w.size(0) : w.size(1);
-  TORCH_CHECK(dbias.is_contiguous() && dbias.numel() == nout, "gemm_dgelu: dbias must hold one fp32 per output column");
-  TORCH_CHECK(F.dim() == 2 && F.size(0) == dy.size(0) && F.size(1) == nout, "gemm_dgelu: F shape");
-  auto C = at::empty({dy.size(0), nout}, dy.options());
-  if (own_gemm(0, trans_w ? 0 : 1, 2, cbf(dy), dy.stride(0), cbf(w), w.stride(0), (int)dy.size(0), (int)nout,
-               (int)dy.size(1), bf(C), C.size(1), nullptr, 0, nullptr, cbf(F), F.size(1), nullptr, 0, f32(dbias),
-               cur_stream(dy)) == 0)
-    return C;
-  auto dg = at::empty_like(C);
-  const Mat A = a_view(dy, false), B = b_view(w, trans_w);
-  gemm_store(A, B, dy, w, bf(dg), dg.size(1), nullptr, nullptr, 0, cur_stream(dy));
-  check(dl_gelu_bwd_colsum(cbf(dg), cbf(F), bf(C), f32(dbias), (int)dg.size(0), (int)dg.size(1), cur_stream(dg)),
-        "gelu_bwd");
-  return C;
+std::tuple<at::Tensor, at::Tensor> gemm_gelu(const at::Tensor& x, const at::Tensor& w, const at::Tensor& bias,
+                                             bool trans_w) {
+  return ffn_up(x, w, bias, trans_w, false);
 }
-
-// FFN-up storing the DERIVATIVE for the backward: G = gelu_new(h), D = gelu_new'(h), h = bf16(x W^T + b)
-// (gemm8 EPI_GELUD; the backward then multiplies by D instead of evaluating gelu_new' — gemm_dmul)
 std::tuple<at::Tensor, at::Tensor> gemm_gelu_d(const at::Tensor& x, const at::Tensor& w, const at::Tensor& bias,
                                                bool trans_w) {
-  expect_operands(x, w);
-  const int64_t nout = trans_w ? w.size(1) : w.size(0);
-  auto D = at::empty({x.size(0), nout}, x.options());
-  auto G = at::empty_like(D);
-  const at::Tensor bias32 = f32_bias(bias, nout);
-  if (use_gemm8() &&
-      took(kGemm8, dl_gemm8(0, trans_w ? 1 : 0, 6, cbf(x), x.stride(0), cbf(w), w.stride(0), (int)x.size(0), (int)nout,
-                            (int)x.size(1), bf(G), G.size(1), nullptr, 0, 0, 0, f32(bias32), nullptr, 0, bf(D),
-                            D.size(1), nullptr, 1, cur_stream(x))) == 0)
-    return {D, G};
-  auto H = at::empty_like(D);
-  const Mat A = a_view(x, false), B = b_view(w, !trans_w);
-  gemm_store(A, B, x, w, bf(H), H.size(1), f32(bias32), nullptr, 0, cur_stream(x));
-  check(dl_gelu_fwd_d(cbf(H), bf(G), bf(D), H.numel(), cur_stream(H)), "gelu_fwd_d");
-  return {D, G};
+  return ffn_up(x, w, bias, trans_w, true);
 }
 
-// FFN dgrad against a stored derivative: C = bf16(dy W) * D, dbias += colsum(C) (gemm8 EPI_DMUL)
-at::Tensor gemm_dmul(const at::Tensor& dy, const at::Tensor& w, const at::Tensor& D, at::Tensor dbias, bool trans_w) {
+// fused FFN dgrad: C = bf16(dy W) * gelu_new'(F) (gemm_dgelu; F the pre-activation) or, with `deriv`,
+// C = bf16(dy W) * F (gemm_dmul, gemm8 only; F the derivative gemm_gelu_d stored); dbias += colsum(C).
+// trans_w: w holds W^T (the forward-layout copy, a K-inner operand for the tiled kernels)
+at::Tensor ffn_dgrad(const char* op, const at::Tensor& dy, const at::Tensor& w, const at::Tensor& F, at::Tensor dbias,
+                     bool trans_w, bool deriv) {
   expect_operands(dy, w);
-  expect(D, at::kBFloat16, "D");
+  expect(F, at::kBFloat16, deriv ? "D" : "F");
   expect(dbias, at::kFloat, "dbias");
   const int64_t nout = trans_w ? w.size(0) : w.size(1);
-  TORCH_CHECK(dbias.is_contiguous() && dbias.numel() == nout, "gemm_dmul: dbias must hold one fp32 per output column");
-  TORCH_CHECK(D.dim() == 2 && D.size(0) == dy.size(0) && D.size(1) == nout, "gemm_dmul: D shape");
+  TORCH_CHECK(dbias.is_contiguous() && dbias.numel() == nout, op, ": dbias must hold one fp32 per output column");
+  TORCH_CHECK(F.dim() == 2 && F.size(0) == dy.size(0) && F.size(1) == nout, op, ": ", deriv ? "D" : "F", " shape");
   auto C = at::empty({dy.size(0), nout}, dy.options());
-  if (use_gemm8() &&
-      took(kGemm8, dl_gemm8(0, trans_w ? 0 : 1, 7, cbf(dy), dy.stride(0), cbf(w), w.stride(0), (int)dy.size(0),
-                            (int)nout, (int)dy.size(1), bf(C), C.size(1), nullptr, 0, 0, 0, nullptr, cbf(D), D.size(1),
-                            nullptr, 0, f32(dbias), 1, cur_stream(dy))) == 0)
-    return C;
-  auto dg = at::empty_like(C);
-  const Mat A = a_view(dy, false), B = b_view(w, trans_w);
-  gemm_store(A, B, dy, w, bf(dg), dg.size(1), nullptr, nullptr, 0, cur_stream(dy));
-  check(dl_mul_colsum(cbf(dg), cbf(D), bf(C), f32(dbias), (int)dg.size(0), (int)dg.size(1), cur_stream(dg)),
-        "mul_colsum");
+  const hipStream_t st = cur_stream(dy);
+  DlGemm g = gemm_desc(dy, false, w, trans_w, bf(C), nout);
+  g.epi = deriv ? DL_EPI_DMUL : DL_EPI_DGELU;
+  g.R = cbf(F), g.ldr = nout;
+  g.dbias = f32(dbias);
+  if (gemm_route(g, deriv ? kUse8 : kUse8 | kUseTiled, dy, st) != kGemmNone) return C;
+  auto dg = at::empty_like(C);  // unfused: the plain store, then the elementwise kernel
+  g.epi = DL_EPI_STORE;
+  g.C = bf(dg), g.R = nullptr, g.dbias = nullptr;
+  gemm_store(g, dy, st);
+  const int M = (int)dg.size(0), N = (int)nout;
+  if (deriv) check(dl_mul_colsum(cbf(dg), cbf(F), bf(C), f32(dbias), M, N, st), "mul_colsum");
+  else check(dl_gelu_bwd_colsum(cbf(dg), cbf(F), bf(C), f32(dbias), M, N, st), "gelu_bwd");
   return C;
+}
+at::Tensor gemm_dgelu(const at::Tensor& dy, const at::Tensor& w, const at::Tensor& F, at::Tensor dbias,
+                      bool trans_w) {
+  return ffn_dgrad("gemm_dgelu", dy, w, F, dbias, trans_w, false);
+}
+at::Tensor gemm_dmul(const at::Tensor& dy, const at::Tensor& w, const at::Tensor& D, at::Tensor dbias, bool trans_w) {
+  return ffn_dgrad("gemm_dmul", dy, w, D, dbias, trans_w, true);
 }
 
 // ------------------------------------------------------------------ SwAV
@@ -1317,11 +1282,6 @@ inline bool few_tile_gemm(int64_t M, int64_t N) { return ((M + 255) / 256) * ((N
 inline at::Tensor rows2d(const at::Tensor& t) {  // channels-last [N, C, H, W] -> [N*H*W, C] view
   return t.permute({0, 2, 3, 1}).reshape({-1, t.size(1)});
 }
-// D[M, N] (bf16, row stride ldd) = A[M, K] . B[N, K]^T
-void gemm_plain(const at::Tensor& a, const at::Tensor& b, bf16_t* d, int64_t ldd, hipStream_t st) {
-  gemm_store(a_view(a, false), b_view(b, true), a, b, d, ldd, nullptr, nullptr, 0, st);
-}
-
 inline DlConvGeom geom(const bf16_t* img, int64_t N, int64_t H, int64_t W, int64_t C, int64_t I, int64_t J,
                        int64_t sh, int64_t sw, int64_t TR, int64_t TS, int64_t dh0, int64_t dhs, int64_t dw0,
                        int64_t dws) {
@@ -1381,8 +1341,9 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
   if (is_pointwise(R, S, stride, pad) && conv_gemm() && !(K <= narrow_1x1_max() && C % 64 == 0) &&
       !(C % 64 == 0 && few_tile_gemm(N * P * Q, K))) {
     const at::Tensor xr = rows2d(x), wr = wk.view({K, C});
-    if (stats) gemm_store_stats(a_view(xr, false), b_view(wr, true), xr, wr, bf(y), K, stats, stat_rows, cur_stream(x));
-    else gemm_plain(xr, wr, bf(y), K, cur_stream(x));
+    const DlGemm g = gemm_desc(xr, false, wr, true, bf(y), K);  // y[M, K] = x[M, C] w[K, C]^T
+    if (stats) gemm_store_stats(g, stats, stat_rows, xr, cur_stream(x));
+    else gemm_store(g, xr, cur_stream(x));
     return y;
   }
   if (C % 64 == 0) {
@@ -1436,8 +1397,9 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
       return y;
     }
   }
-  if (stats) gemm_store_stats(a_view(col, false), b_view(wp, true), col, wp, bf(y), K, stats, stat_rows, cur_stream(x));
-  else gemm_plain(col, wp, bf(y), K, cur_stream(x));
+  const DlGemm g = gemm_desc(col, false, wp, true, bf(y), K);
+  if (stats) gemm_store_stats(g, stats, stat_rows, col, cur_stream(x));
+  else gemm_store(g, col, cur_stream(x));
   return y;
 }
 
@@ -1588,8 +1550,9 @@ at::Tensor conv2d_dgrad(const at::Tensor& dy_in, const at::Tensor& w, int64_t st
       !(C <= narrow_1x1_max() && K % 64 == 0)) {
     // dX[M, C] = dY[M, K] W[K, C] (+ residual): the weight as a K-outer B operand, no transposed copy
     const at::Tensor dyr = rows2d(dy), wkc = wk.view({K, C});
-    gemm_store(a_view(dyr, false), b_view(wkc, false), dyr, wkc, bf(dx), C, nullptr,
-               residual.has_value() ? cbf(*residual) : nullptr, C, cur_stream(dy));
+    DlGemm g = gemm_desc(dyr, false, wkc, false, bf(dx), C);
+    if (residual.has_value()) g.R = cbf(*residual), g.ldr = C;
+    gemm_store(g, dyr, cur_stream(dy));
     return dx;
   }
   conv_dgrad_classes(dy, wk, stride, pad, H, W, dx, wds, nullptr, 1, nullptr);
@@ -1601,7 +1564,7 @@ at::Tensor conv2d_dgrad(const at::Tensor& dy_in, const at::Tensor& w, int64_t st
 // backward (which then skips its statistics pass, bn_bwd(stats_ready)): returns g = dX (+ residual)
 // masked by the ReLU — mask from y > 0 when y is given (the BN had a residual branch), else from
 // the forward's pre-activation over x (the BN input) — and adds sums[grp][c] += g, sums[grp][C + c]
-// += g * (x - mean) * rstd, in the GEMM epilogue of a 1x1 stride-1 data gradient (gemm8 EPI 5)
+// += g * (x - mean) * rstd, in the GEMM epilogue of a 1x1 stride-1 data gradient (gemm8 DL_EPI_BNBWD)
 // or in conv.hip's epilogue on every
 // parity class of the others (no residual; whole 256-row tiles per statistics group).  Returns
 // (dx, fused): where the epilogue cannot take it, dx is the plain data gradient (+ residual), unmasked, and fused is false —
@@ -1639,14 +1602,12 @@ std::tuple<at::Tensor, bool> conv2d_dgrad_bn(const at::Tensor& dy, const at::Ten
     auto dx = at::empty_like(x);
     const at::Tensor wk = krsc_view(w);
     const at::Tensor dyr = rows2d(gdy), wkc = wk.view({K, C});
-    const Mat A = a_view(dyr, false), B = b_view(wkc, false);
-    const bf16_t* rp = residual.has_value() ? cbf(*residual) : nullptr;
-    const int M = (int)A.rows;
-    const hipStream_t st = cur_stream(dy);
-    if (use_gemm8() && dl_gemm8(A.kouter, B.kouter, 5, cbf(dyr), A.ld, cbf(wkc), B.ld, M, (int)C, (int)A.k, bf(dx), C,
-                                nullptr, 0, 0, 0, nullptr, rp, C, nullptr, 0, nullptr, 1, st, f32(sums), stat_rows,
-                                &bn) == 0)
-      return {dx, true};
+    DlGemm g = gemm_desc(dyr, false, wkc, false, bf(dx), C);
+    g.epi = DL_EPI_BNBWD;
+    if (residual.has_value()) g.R = cbf(*residual), g.ldr = C;
+    g.stats = f32(sums), g.stat_rows = stat_rows;
+    g.bn = &bn;
+    if (gemm_route(g, kUse8, dyr, cur_stream(dy)) != kGemmNone) return {dx, true};
   }
   // 3x3 / strided data gradients (Bottleneck conv2 <- bn1) and the 1x1 ones gemm8 does not take
   // (at most 128 input channels: conv3 <- bn2 in the first stages): conv.hip's epilogue
@@ -1802,4 +1763,5 @@ extern "C" int dedloc_amd_native_abi_version() { return 1; }
 TORCH_LIBRARY(dedloc_ws, m) {
   m.def("clear_workspaces() -> int", &clear_workspaces);
   m.def("gemm_backend_counts() -> int[]", &gemm_backend_counts);
+  m.def("gemm_wgrad_splits(int M, int N, int K) -> int", &gemm_wgrad_splits);
 }

@@ -86,13 +86,8 @@ int dl_xent_fwd_bwd(const bf16_t* logits, const long* labels, bf16_t* dlogits, f
 int dl_xent_eval(const bf16_t* logits, const long* labels, float* row_loss, int* row_rank, int M, int V, long ld,
                  int ignore_index, hipStream_t st);
 
-// gemm.hip  (epi: 0 store(+bias,+residual), 1 bias+gelu (H and gelu(H)), 2 dgelu(+colsum), 3 fp32 +=)
-int dl_gemm(int a_kouter, int b_kouter, int epi, const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N,
-            int K, bf16_t* C, long ldc, float* Cf, long ldcf, const float* bias, const bf16_t* R, long ldr, bf16_t* H,
-            long ldh, float* dbias, int splits, hipStream_t st);
-
-// BatchNorm+ReLU backward preparation fused into a data-gradient GEMM epilogue (gemm8 EPI 5,
-// gemm_small): the GEMM's output is dY of the BN's output; the epilogue masks it by the ReLU
+// BatchNorm+ReLU backward preparation fused into a data-gradient GEMM epilogue (gemm8
+// DL_EPI_BNBWD, gemm_small): the GEMM's output is dY of the BN's output; the epilogue masks it by the ReLU
 // (Y > 0, or the forward's pre-activation X*gamma*rstd + beta - mean*gamma*rstd > 0 when Y is null),
 // stores the masked g and accumulates stats[m / stat_rows][n] += g and [N + n] += g*(X - mean)*rstd.
 struct DlBnBwdEpi {
@@ -105,13 +100,44 @@ struct DlBnBwdEpi {
   const float* beta;    // [N]
 };
 
-// gemm8.hip (LDS-DMA 8-phase MFMA GEMM; epi as dl_gemm; EPI 3 writes fp32 slab blockIdx.y of
-// Cf (+= when accumulate); splits > 1 only for EPI 3; EPI 4 = EPI 0 plus BatchNorm statistics of
-// the stored values: stats[m / stat_rows][0..N) += column sums, [N..2N) += sums of squares)
-int dl_gemm8(int a_kouter, int b_kouter, int epi, const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N,
-             int K, bf16_t* C, long ldc, float* Cf, long ldcf, long slab, int accumulate, const float* bias,
-             const bf16_t* R, long ldr, bf16_t* H, long ldh, float* dbias, int splits, hipStream_t st,
-             float* stats = nullptr, long stat_rows = 0, const DlBnBwdEpi* bn = nullptr);
+// The epilogues of the three GEMM kernels.  gemm8.hip has all eight, gemm.hip the first four,
+// gemm_small.hip STORE and F32 (a launcher returns -1 for an epilogue it does not have).
+enum DlGemmEpi {
+  DL_EPI_STORE = 0,  // C = acc (+ bias[n]) (+ R[m, n])
+  DL_EPI_GELU = 1,   // H = bf16(acc + bias), C = gelu_new(H)
+  DL_EPI_DGELU = 2,  // C = bf16(acc) * gelu_new'(R[m, n]); dbias[n] += sum_m C
+  DL_EPI_F32 = 3,    // Cf (+)= acc (fp32)
+  DL_EPI_STATS = 4,  // STORE plus BatchNorm statistics of the stored values:
+                     // stats[m / stat_rows][0..N) += column sums, [N..2N) += sums of squares
+  DL_EPI_BNBWD = 5,  // DlBnBwdEpi
+  DL_EPI_GELUD = 6,  // h = bf16(acc + bias), C = gelu_new(h), H = gelu_new'(h)
+  DL_EPI_DMUL = 7,   // C = bf16(acc) * R[m, n] (R as stored by GELUD); dbias[n] += sum_m C
+};
+
+// One product C = op(A) op(B) with its epilogue.  An operand is [rows, K] with leading dimension
+// ld: K-inner (kouter = 0) holds element (r, k) at p[r * ld + k], K-outer at p[k * ld + r].
+struct DlGemm {
+  const bf16_t* A = nullptr; long lda = 0; int a_kouter = 0;  // [M, K]
+  const bf16_t* B = nullptr; long ldb = 0; int b_kouter = 0;  // [N, K]
+  int M = 0, N = 0, K = 0;
+  DlGemmEpi epi = DL_EPI_STORE;
+  bf16_t* C = nullptr; long ldc = 0;  // bf16 output (every epilogue but F32)
+  // F32 output.  gemm8 writes reduction split z to Cf + z * slab (+= when accumulate); gemm.hip
+  // always adds (atomics when split); gemm_small adds when accumulate
+  float* Cf = nullptr; long ldcf = 0; long slab = 0; int accumulate = 0;
+  const float* bias = nullptr;            // fp32 [N]
+  const bf16_t* R = nullptr; long ldr = 0;  // residual (STORE, BNBWD), pre-activation (DGELU), derivative (DMUL)
+  bf16_t* H = nullptr; long ldh = 0;        // second bf16 output (GELU, GELUD)
+  float* dbias = nullptr;                 // fp32 [N], accumulated (DGELU, DMUL)
+  int splits = 1;  // reduction split: gemm8 (F32 only), gemm.hip (F32), gemm_small (slabs in `ws`)
+  float* stats = nullptr; long stat_rows = 0;  // STATS, BNBWD; gemm_small: with STORE, unsplit only
+  const DlBnBwdEpi* bn = nullptr;              // BNBWD; gemm_small: with STORE and stats
+};
+
+// gemm8.hip (LDS-DMA 8-phase MFMA GEMM, every epilogue), gemm.hip (register-staged 256x256 tiles,
+// STORE / GELU / DGELU / F32)
+int dl_gemm8(const DlGemm& g, hipStream_t st);
+int dl_gemm(const DlGemm& g, hipStream_t st);
 
 // swav.hip
 int dl_sinkhorn_ws(int n, int K);
@@ -155,7 +181,7 @@ struct DlConvGeom {
   int TR, TS, dh0, dhs, dw0, dws;
 };
 // out[(n, i*osh+oh0, j*osw+ow0), 0..N) (NHWC, row stride ldo) = sum_{t,c} img(pixel(m,t), c) * w[n][t*C + c]
-// stats (optional): BatchNorm statistics of the stored output as in dl_gemm8 EPI 4 (stat_rows a
+// stats (optional): BatchNorm statistics of the stored output as DL_EPI_STATS (stat_rows a
 // multiple of 128 dividing M; -1 otherwise)
 int dl_conv_fwd(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, int osh, int osw,
                 int oh0, int ow0, long ldo, hipStream_t st, float* stats = nullptr, long stat_rows = 0,
@@ -235,16 +261,13 @@ int dl_avgpool_bwd(const bf16_t* dy, bf16_t* dx, int N, int HW, int C, hipStream
 int dl_l2norm_fwd(const bf16_t* x, bf16_t* y, float* rinv, int rows, int D, float eps, hipStream_t st);
 int dl_l2norm_bwd(const bf16_t* dy, const bf16_t* y, const float* rinv, bf16_t* dx, int rows, int D, hipStream_t st);
 
-// gemm_small.hip: any-shape / any-stride bf16 MFMA GEMM (epi 0: bf16 C (+bias)(+R); 1: fp32 Cf (+)=).
-// splits > 1 splits the reduction into fp32 slabs: ws must hold splits * M * N floats.
+// gemm_small.hip: any-shape / any-stride bf16 MFMA GEMM (STORE: bf16 C (+bias)(+R); F32: fp32 Cf (+)=).
+// g.splits > 1 splits the reduction into fp32 slabs: ws must hold splits * M * N floats.
+// stats (STORE, splits 1 only): BatchNorm statistics of the stored values as DL_EPI_STATS
+// (stat_rows a multiple of 128 dividing M)
+int dl_gemm_small(const DlGemm& g, float* ws, hipStream_t st);
 int dl_gemm_small_splits(int M, int N, int K);
 // batch GEMMs in one launch (entry b: A + b*sab, B + b*sbb, C / Cf + b*scb); epi 0 bf16, 1 fp32 (=)
 int dl_gemm_small_batched(int epi, const bf16_t* A, long sam, long sak, long sab, const bf16_t* B, long sbn, long sbk,
                           long sbb, int M, int N, int K, bf16_t* C, long ldc, float* Cf, long ldcf, long scb,
                           int batch, hipStream_t st);
-// stats (epi 0, splits 1 only): BatchNorm statistics of the stored values as in dl_gemm8 EPI 4
-// (stat_rows a multiple of 128 dividing M)
-int dl_gemm_small(int epi, const bf16_t* A, long sam, long sak, const bf16_t* B, long sbn, long sbk, int M, int N,
-                  int K, bf16_t* C, long ldc, float* Cf, long ldcf, int accumulate, const float* bias, const bf16_t* R,
-                  long ldr, int splits, float* ws, hipStream_t st, float* stats = nullptr, long stat_rows = 0,
-                  const DlBnBwdEpi* bn = nullptr);

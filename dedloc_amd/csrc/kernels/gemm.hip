@@ -28,7 +28,7 @@ typedef short s4_t __attribute__((ext_vector_type(4)));
 typedef short s8_t __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) s4_t lds_s4;
 
-enum { EPI_STORE = 0, EPI_GELU = 1, EPI_DGELU = 2, EPI_ACC32 = 3 };
+enum { EPI_STORE = DL_EPI_STORE, EPI_GELU = DL_EPI_GELU, EPI_DGELU = DL_EPI_DGELU, EPI_ACC32 = DL_EPI_F32 };
 
 constexpr int BM = 256, BN = 256, BK = 64;
 constexpr int NTHREADS = 512;
@@ -280,23 +280,26 @@ int launch(const GemmArgs& a, int splits, hipStream_t st) {
 
 }  // namespace
 
-// Returns -1 when the shape is not supported by the MFMA kernel (caller falls back to the library):
-// the reduction extent must be a multiple of 64 (per split), K-outer operands need their row extent
-// (M or N) to be a multiple of 256 and ld a multiple of 8.
-int dl_gemm(int a_kouter, int b_kouter, int epi, const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N,
-            int K, bf16_t* C, long ldc, float* Cf, long ldcf, const float* bias, const bf16_t* R, long ldr, bf16_t* H,
-            long ldh, float* dbias, int splits, hipStream_t st) {
+// Returns -1 when the shape or the epilogue is outside the kernel's contract (the binding layer then
+// tries gemm_small.hip or raises; there is no library path): the reduction extent must be a multiple
+// of 64 (per split), K-outer operands need their row extent (M or N) to be a multiple of 256 and ld
+// a multiple of 8.  Reads no slab / accumulate / stats / bn field of the descriptor: its F32 form adds
+// into Cf.
+int dl_gemm(const DlGemm& g, hipStream_t st) {
+  const int M = g.M, N = g.N, K = g.K, epi = g.epi;
+  int splits = g.splits;
   if (K % BK || M <= 0 || N <= 0) return -1;
-  if (lda % 8 || ldb % 8) return -1;
-  if (a_kouter && M % BM) return -1;
-  if (b_kouter && N % BN) return -1;
+  if (g.lda % 8 || g.ldb % 8) return -1;
+  if (g.a_kouter && M % BM) return -1;
+  if (g.b_kouter && N % BN) return -1;
   if (splits < 1) splits = 1;
   // the splits must tile K exactly, in whole K-tiles: splits * k_per_split == K.  (K / splits) % BK
   // alone lets K = 66624, splits = 65 through (1024 rows per split) and drops the last 64 rows.
   while (splits > 1 && K % (splits * BK)) --splits;
-  GemmArgs a{A, lda, B, ldb, M, N, K, C, ldc, Cf, ldcf, bias, R, ldr, H, ldh, dbias, K / splits};
+  GemmArgs a{g.A, g.lda, g.B, g.ldb, M, N, K, g.C, g.ldc, g.Cf, g.ldcf, g.bias, g.R, g.ldr, g.H, g.ldh, g.dbias,
+             K / splits};
 #define DL_GEMM_CASE(AK, BK_, E) \
-  if (a_kouter == AK && b_kouter == BK_ && epi == E) return launch<AK, BK_, E>(a, splits, st);
+  if (g.a_kouter == AK && g.b_kouter == BK_ && epi == E) return launch<AK, BK_, E>(a, splits, st);
   DL_GEMM_CASE(0, 0, EPI_STORE)
   DL_GEMM_CASE(0, 0, EPI_GELU)
   DL_GEMM_CASE(0, 1, EPI_STORE)

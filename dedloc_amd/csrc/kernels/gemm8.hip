@@ -62,8 +62,9 @@ typedef short s4_t __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) s4_t lds_s4;
 typedef __attribute__((address_space(3))) void lds_void;
 
-enum { EPI_STORE = 0, EPI_GELU = 1, EPI_DGELU = 2, EPI_F32 = 3, EPI_STATS = 4, EPI_BNBWD = 5, EPI_GELUD = 6,
-       EPI_DMUL = 7 };
+// the kernel's template argument stays an int: the values are DlGemmEpi's (dl_kernels.h)
+enum { EPI_STORE = DL_EPI_STORE, EPI_GELU = DL_EPI_GELU, EPI_DGELU = DL_EPI_DGELU, EPI_F32 = DL_EPI_F32,
+       EPI_STATS = DL_EPI_STATS, EPI_BNBWD = DL_EPI_BNBWD, EPI_GELUD = DL_EPI_GELUD, EPI_DMUL = DL_EPI_DMUL };
 
 constexpr int BM = 256, BN = 256, BK = 64, NT = 512;
 constexpr int HALF = 16384;     // one half-tile image
@@ -737,25 +738,25 @@ inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 
 // Returns -1 when the shape is outside the kernel's contract: N % 256 == 0, K % (64 * splits) == 0,
 // a K-outer A needs M % 256 == 0, every leading dimension a multiple of 8 elements and every base
 // pointer 16-byte aligned.
-int dl_gemm8(int a_kouter, int b_kouter, int epi, const bf16_t* A, long lda, const bf16_t* B, long ldb, int M, int N,
-             int K, bf16_t* C, long ldc, float* Cf, long ldcf, long slab, int accumulate, const float* bias,
-             const bf16_t* R, long ldr, bf16_t* H, long ldh, float* dbias, int splits, hipStream_t st, float* stats,
-             long stat_rows, const DlBnBwdEpi* bn) {
+int dl_gemm8(const DlGemm& g, hipStream_t st) {
+  const int M = g.M, N = g.N, K = g.K, splits = g.splits, epi = g.epi;
   if (M <= 0 || N <= 0 || K <= 0 || splits < 1) return -1;
   if (N % BN || K % (BK * splits)) return -1;
-  if (a_kouter && M % BM) return -1;
-  if (lda % 8 || ldb % 8 || !aligned16(A) || !aligned16(B)) return -1;
+  if (g.a_kouter && M % BM) return -1;
+  if (g.lda % 8 || g.ldb % 8 || !aligned16(g.A) || !aligned16(g.B)) return -1;
   if (epi == EPI_F32) {
-    if (!Cf || ldcf % 4 || !aligned16(Cf) || slab % 4) return -1;
+    if (!g.Cf || g.ldcf % 4 || !aligned16(g.Cf) || g.slab % 4) return -1;
   } else {
-    if (!C || ldc % 8 || !aligned16(C)) return -1;
-    if (R && (ldr % 8 || !aligned16(R))) return -1;
-    if ((epi == EPI_GELU || epi == EPI_GELUD) && (!H || ldh % 8 || !aligned16(H))) return -1;
-    if ((epi == EPI_DGELU || epi == EPI_DMUL) && !R) return -1;
+    if (!g.C || g.ldc % 8 || !aligned16(g.C)) return -1;
+    if (g.R && (g.ldr % 8 || !aligned16(g.R))) return -1;
+    if ((epi == EPI_GELU || epi == EPI_GELUD) && (!g.H || g.ldh % 8 || !aligned16(g.H))) return -1;
+    if ((epi == EPI_DGELU || epi == EPI_DMUL) && !g.R) return -1;
     if (splits != 1) return -1;
     // EPI_STATS: every 256-row tile inside one statistics group
-    if ((epi == EPI_STATS || epi == EPI_BNBWD) && (!stats || stat_rows < BM || stat_rows % BM || M % stat_rows))
+    if ((epi == EPI_STATS || epi == EPI_BNBWD) &&
+        (!g.stats || g.stat_rows < BM || g.stat_rows % BM || M % g.stat_rows))
       return -1;
+    const DlBnBwdEpi* bn = g.bn;
     if (epi == EPI_BNBWD && (!bn || !bn->X || bn->ldx % 8 || !aligned16(bn->X) || (bn->Y && !aligned16(bn->Y)) ||
                              (!bn->Y && (!bn->gamma || !bn->beta))))
       return -1;
@@ -764,11 +765,11 @@ int dl_gemm8(int a_kouter, int b_kouter, int epi, const bf16_t* A, long lda, con
   // 1507 -> 1468 us, FFN-up + GELU 2409 -> 2324 us, FFN-down data gradient 2027 -> 1970 us, the rest
   // within +-1.5% (profiles/r3_gemm8_tile_order_T262144.jsonl)
   constexpr int group_m = 4;
-  Args a{A, lda, B, ldb, M, N, K / splits, C, ldc, Cf, ldcf, slab, accumulate, bias, R, ldr, H, ldh, dbias,
-         stats, stat_rows, DlBnBwdEpi{}, group_m};
-  if (epi == EPI_BNBWD) a.bn = *bn;  // by value: the kernel reads it from its argument buffer
+  Args a{g.A, g.lda, g.B, g.ldb, M, N, K / splits, g.C, g.ldc, g.Cf, g.ldcf, g.slab, g.accumulate, g.bias, g.R, g.ldr,
+         g.H, g.ldh, g.dbias, g.stats, g.stat_rows, DlBnBwdEpi{}, group_m};
+  if (epi == EPI_BNBWD) a.bn = *g.bn;  // by value: the kernel reads it from its argument buffer
 #define DL_GEMM8_CASE(AK, BK_, E) \
-  if (a_kouter == AK && b_kouter == BK_ && epi == E) return launch8<AK, BK_, E>(a, splits, st);
+  if (g.a_kouter == AK && g.b_kouter == BK_ && epi == E) return launch8<AK, BK_, E>(a, splits, st);
   DL_GEMM8_CASE(0, 0, EPI_STORE)
   DL_GEMM8_CASE(0, 0, EPI_GELU)
   DL_GEMM8_CASE(0, 1, EPI_STORE)

@@ -362,41 +362,46 @@ int dl_gemm_small_splits(int M, int N, int K) {
   return (K + kchunk - 1) / kchunk;
 }
 
-int dl_gemm_small(int epi, const bf16_t* A, long sam, long sak, const bf16_t* B, long sbn, long sbk, int M, int N,
-                  int K, bf16_t* C, long ldc, float* Cf, long ldcf, int accumulate, const float* bias, const bf16_t* R,
-                  long ldr, int splits, float* ws, hipStream_t st, float* stats, long stat_rows,
-                  const DlBnBwdEpi* bn) {
+// STORE and F32 only (the kernel's EPI 0 and 1; -1 for the others).  The element strides follow from
+// kouter / ld, so one of each operand's two is 1.
+int dl_gemm_small(const DlGemm& g, float* ws, hipStream_t st) {
+  if (g.epi != DL_EPI_STORE && g.epi != DL_EPI_F32) return -1;
+  const int epi = g.epi == DL_EPI_STORE ? 0 : 1;
+  const int M = g.M, N = g.N, K = g.K, splits = g.splits;
+  const DlBnBwdEpi* bn = g.bn;
   if (M <= 0 || N <= 0 || K <= 0 || splits < 1) return -1;
-  if (stats && (epi != 0 || splits != 1 || stat_rows < TM || stat_rows % TM || M % stat_rows)) return -1;
-  if (bn && (!stats || !bn->X || (!bn->Y && (!bn->gamma || !bn->beta)))) return -1;
-  if (epi == 0 && !C) return -1;
-  if (epi == 1 && !Cf) return -1;
+  if (g.stats && (epi != 0 || splits != 1 || g.stat_rows < TM || g.stat_rows % TM || M % g.stat_rows)) return -1;
+  if (bn && (!g.stats || !bn->X || (!bn->Y && (!bn->gamma || !bn->beta)))) return -1;
+  if (epi == 0 && !g.C) return -1;
+  if (epi == 1 && !g.Cf) return -1;
   if (splits > 1 && !ws) return -1;
   const int kchunk = splits > 1 ? ((K + splits - 1) / splits + TK - 1) / TK * TK : K;
   const int S = (K + kchunk - 1) / kchunk;
   const int tn = N <= 64 ? 64 : 128;
   if ((M + TM - 1) / TM > 65535 || S > 65535) return -1;
+  const long sam = g.a_kouter ? 1 : g.lda, sak = g.a_kouter ? g.lda : 1;
+  const long sbn = g.b_kouter ? 1 : g.ldb, sbk = g.b_kouter ? g.ldb : 1;
   int LA, LB;
   bool VA, VB;
-  walk(A, sam, sak, &LA, &VA);
-  walk(B, sbn, sbk, &LB, &VB);
+  walk(g.A, sam, sak, &LA, &VA);
+  walk(g.B, sbn, sbk, &LB, &VB);
   if (S == 1) {
-    SmallArgs a{A, sam, sak, B, sbn, sbk, M, N, K, kchunk, C, ldc, Cf, ldcf, 0, accumulate, bias, R, ldr, stats,
-                stat_rows, bn ? *bn : DlBnBwdEpi{}, bn ? 1 : 0, 0, 0, 0, 0};
+    SmallArgs a{g.A, sam, sak, g.B, sbn, sbk, M, N, K, kchunk, g.C, g.ldc, g.Cf, g.ldcf, 0, g.accumulate, g.bias, g.R,
+                g.ldr, g.stats, g.stat_rows, bn ? *bn : DlBnBwdEpi{}, bn ? 1 : 0, 0, 0, 0, 0};
     if (epi == 0) launch_tn<0>(a, LA, VA, LB, VB, tn, 1, st);
     else launch_tn<1>(a, LA, VA, LB, VB, tn, 1, st);
     return 0;
   }
   if (bn) return -1;  // the BN preparation needs the single-pass (unsplit) epilogue
-  SmallArgs a{A, sam, sak, B, sbn, sbk, M, N, K, kchunk, nullptr, 0, ws, N, (long)M * N, 0, nullptr, nullptr, 0,
+  SmallArgs a{g.A, sam, sak, g.B, sbn, sbk, M, N, K, kchunk, nullptr, 0, ws, N, (long)M * N, 0, nullptr, nullptr, 0,
               nullptr, 0, DlBnBwdEpi{}, 0, 0, 0, 0, 0};
   launch_tn<1>(a, LA, VA, LB, VB, tn, S, st);
   const long total = (long)M * N;
   const int blocks = (int)std::min<long>((total + 255) / 256, 4096);
   if (epi == 0)
-    slab_finish_kernel<true><<<blocks, 256, 0, st>>>(ws, S, M, N, C, ldc, bias, R, ldr, nullptr, 0, 0);
+    slab_finish_kernel<true><<<blocks, 256, 0, st>>>(ws, S, M, N, g.C, g.ldc, g.bias, g.R, g.ldr, nullptr, 0, 0);
   else
-    slab_finish_kernel<false><<<blocks, 256, 0, st>>>(ws, S, M, N, nullptr, 0, nullptr, nullptr, 0, Cf, ldcf,
-                                                      accumulate);
+    slab_finish_kernel<false><<<blocks, 256, 0, st>>>(ws, S, M, N, nullptr, 0, nullptr, nullptr, 0, g.Cf, g.ldcf,
+                                                      g.accumulate);
   return 0;
 }

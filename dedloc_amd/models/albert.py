@@ -150,7 +150,7 @@ _DGRAD_WT = True
 _SHARED_WGRAD = True
 # The FFN-up epilogue stores gelu_new'(h) (bf16) for the backward instead of the pre-activation h:
 # it shares the forward's exp2 / rcp, and the FFN-down data gradient's epilogue becomes one multiply
-# instead of a second sigmoid evaluation per element (gemm_gelu_d / gemm_dmul, gemm8 EPI 6 / 7).
+# instead of a second sigmoid evaluation per element (gemm_gelu_d / gemm_dmul, gemm8 DL_EPI_GELUD / DL_EPI_DMUL).
 _GELU_GRAD_IN_FWD = True
 
 

@@ -32,6 +32,7 @@ GEMM8_DEPTH_SHAPES = tuple((256, 256, k) for k in (64, 128, 192, 256, 320))
 GEMM8_ORDER_SHAPES = ((1025, 256, 64), (1300, 768, 128), (1537, 768, 64), (1800, 512, 64))
 FUSED_SHAPES = ((300, 256, 128), (257, 512, 64), (1025, 256, 192))
 FUSED_N384_SHAPES = tuple((300, 384, k) for k in (64, 128))
+FUSED_NARROW_SHAPES = ((256, 128, 64),)
 # weight gradients: (tokens, rows of c, columns of c, split count wgrad_splits8 gives)
 WGRAD_TN = ((64, 256, 256, 1), (512, 256, 256, 2), (1344, 256, 256, 3), (4096, 512, 256, 16),
             (25088, 256, 256, 49))

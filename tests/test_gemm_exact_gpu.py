@@ -58,11 +58,16 @@ def test_gemm8_store_tile_order(cuda, O):
 
 
 # ------------------------------------------------------------------------------------------------ fused epilogues
-def _fused_backend(N, k_inner_b):
+def _fused_backend(N, k_inner_b, own_epilogue=True):
     """gemm8 inside its contract (N % 256 == 0); else gemm.hip takes a K-inner B (fused bias + GELU, or
-    the plain store of the unfused pair) and gemm_small a K-outer B whose N is no multiple of 256."""
+    the plain store of the unfused pair) and gemm_small a K-outer B whose N is no multiple of 256.
+    An output of at most 192 columns reaches gemm.hip only through an epilogue gemm.hip has itself for
+    that layout (bias + GELU with a K-inner B; its GELU' form wants a K-outer B, hence N % 256 == 0):
+    the plain store of that width goes to gemm_small's narrower tiles."""
     if N % 256 == 0:
         return "gemm8"
+    if N <= 192 and not own_epilogue:
+        return "gemm_small"
     return "gemm" if k_inner_b else "gemm_small"
 
 
@@ -81,7 +86,7 @@ def check_fused(O, cuda, shapes):
                     H, G = O.gemm_gelu(p.a, w, p.bias, trans_w)
                 gc.expect_exact(H, ref, f"gemm_gelu H {tag}", tile=gc.TILE)
                 gc.expect_ulp(G, gc.gelu_new64(H), f"gemm_gelu G {tag}")
-                with gc.took(f"gemm_gelu_d {tag}", **{_fused_backend(N, not trans_w): 1}):
+                with gc.took(f"gemm_gelu_d {tag}", **{_fused_backend(N, not trans_w, False): 1}):
                     D, G = O.gemm_gelu_d(p.a, w, p.bias, trans_w)
                 h = ref.float().bfloat16()
                 gc.expect_ulp(G, gc.gelu_new64(h), f"gemm_gelu_d G {tag}")
@@ -94,13 +99,13 @@ def check_fused(O, cuda, shapes):
                 pre = gc.grid_values((N,), 8, seed=3, grid=1.0, dtype=torch.float32, device=cuda)
                 F = gc.grid_values((M, N), 16, seed=4, device=cuda)
                 dbias = pre.clone()
-                with gc.took(f"gemm_dgelu {tag}", **{_fused_backend(N, trans_w): 1}):
+                with gc.took(f"gemm_dgelu {tag}", **{_fused_backend(N, trans_w, False): 1}):
                     C = O.gemm_dgelu(q.a, w, F, dbias, trans_w)
                 gc.expect_ulp(C, dg * gc.gelu_new_grad64(F), f"gemm_dgelu C {tag}")
                 gc.expect_colsum(dbias, pre, C, f"gemm_dgelu dbias {tag}")
                 Dm = gc.grid_values((M, N), 6, seed=5, device=cuda)
                 dbias = pre.clone()
-                with gc.took(f"gemm_dmul {tag}", **{_fused_backend(N, trans_w): 1}):
+                with gc.took(f"gemm_dmul {tag}", **{_fused_backend(N, trans_w, False): 1}):
                     C = O.gemm_dmul(q.a, w, Dm, dbias, trans_w)
                 gc.expect_exact(C, dg * Dm.double(), f"gemm_dmul C {tag}", tile=gc.TILE)
                 gc.expect_colsum(dbias, pre, C, f"gemm_dmul dbias {tag}")
@@ -114,6 +119,12 @@ def test_fused_ops_outside_gemm8_contract(cuda, O):
     """N = 384: gemm.hip or the unfused pair (store + gelu_fwd / gelu_fwd_d / gelu_bwd_colsum /
     mul_colsum); the column-sum kernels on a row tail and a partial 512-column block"""
     check_fused(O, cuda, gc.FUSED_N384_SHAPES)
+
+
+def test_fused_ops_on_a_narrow_output(cuda, O):
+    """N = 128, K = 64: gemm8 refuses all four; gemm.hip fuses bias + GELU for a K-inner weight; every
+    other form is the unfused pair, whose store goes to gemm_small (N <= 192)"""
+    check_fused(O, cuda, gc.FUSED_NARROW_SHAPES)
 
 
 # ------------------------------------------------------------------------------------------------ weight gradients
@@ -169,6 +180,19 @@ def test_gemm8_shared_weight_gradient_series(cuda, O):
             gc.expect_exact(c, want, f"gemm_acc_f32_shared series {series}", tile=gc.TILE)
     finally:
         torch.ops.dedloc_ws.clear_workspaces()
+
+
+# (M, N, K) of c [M, N] += over K tokens -> the split count of gemm8's weight gradient on 256 CUs
+WGRAD_SPLITS = {(3072, 1024, 262144): 16, (1024, 1024, 262144): 16, (4096, 1024, 262144): 4, (1024, 4096, 262144): 4,
+                (256, 256, 25088): 49, (512, 512, 25088): 49, (2048, 512, 25088): 14, (256, 256, 3136): 7,
+                (768, 256, 1024): 4, (256, 256, 512): 2, (256, 256, 256): 1, (256, 256, 64): 1,
+                (256, 256, 100): 1}  # the last: K no multiple of 64
+
+
+def test_gemm_wgrad_split_table(O):
+    """host arithmetic only (nothing is launched): the split choice stays what it was"""
+    got = {s: int(torch.ops.dedloc_ws.gemm_wgrad_splits(*s)) for s in WGRAD_SPLITS}
+    assert got == WGRAD_SPLITS
 
 
 # ------------------------------------------------------------------------------------------------ gemm.hip

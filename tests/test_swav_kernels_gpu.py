@@ -4,6 +4,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_checks
+
 pytestmark = pytest.mark.gpu
 
 
@@ -175,7 +177,7 @@ def test_conv_dgrad_residual_epilogue(cuda, cin, cout):
 
 
 @pytest.mark.parametrize("cin,cout,k,stride,N,ymask,res,expect_fused", [
-    (64, 256, 1, 1, 4, False, False, True),    # bn2 -> conv3 (1x1 on conv.hip / gemm_small, N=64)
+    (64, 256, 1, 1, 4, False, False, True),    # bn2 -> conv3 (1x1 on conv.hip's epilogue: N=64 is outside gemm8)
     (256, 1024, 1, 1, 4, False, False, True),  # bn2 -> conv3 (gemm8, N=256)
     (256, 64, 1, 1, 4, True, True, True),      # bn3 -> next conv1 (gemm8, N=256)
     (64, 64, 3, 1, 4, False, False, True),     # bn1 -> conv2 3x3 (conv.hip epilogue, 256x64 tiles)
@@ -185,7 +187,8 @@ def test_conv_dgrad_bn_matches_reference(cuda, cin, cout, k, stride, N, ymask, r
     """conv2d_dgrad_bn (BN+ReLU backward preparation in the data-gradient epilogue; where it reports
     not fused, the plain gradient followed by the separate bn_bwd_prep pass) against plain fp32
     PyTorch: the data gradient (+ residual) masked by the BN+ReLU's live outputs, and the BN
-    backward's two per-group column sums."""
+    backward's two per-group column sums.  The 1x1 cases with 256 input channels run gemm8's BNBWD
+    epilogue (one counted launch); every other case runs on conv.hip, which the GEMM counters do not see."""
     torch.manual_seed(7)
     CLF = torch.channels_last
     G, H = 2, 16
@@ -199,7 +202,8 @@ def test_conv_dgrad_bn_matches_reference(cuda, cin, cout, k, stride, N, ymask, r
     rstd = torch.rand(G, cin, device=cuda) + 0.5
     gamma, beta = torch.rand(cin, device=cuda) + 0.5, torch.randn(cin, device=cuda) * 0.1
     sums = torch.zeros(G * 2 * cin, device=cuda)
-    g, fused = torch.ops.dedloc.conv2d_dgrad_bn(dy, w, stride, k // 2, H, H, r, x, y, mean, rstd, gamma, beta, sums, G)
+    with gemm_checks.took(f"conv2d_dgrad_bn cin={cin} k={k}", gemm8=1 if (k == 1 and cin == 256) else 0):
+        g, fused = torch.ops.dedloc.conv2d_dgrad_bn(dy, w, stride, k // 2, H, H, r, x, y, mean, rstd, gamma, beta, sums, G)
     assert fused == expect_fused
     if not fused:
         g = torch.ops.dedloc.bn_bwd_prep(g, x, y, mean, rstd, gamma, beta, sums, G)
