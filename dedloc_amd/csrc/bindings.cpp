@@ -416,6 +416,61 @@ std::tuple<at::Tensor, at::Tensor> xent_eval(const at::Tensor& logits, const at:
   return {row_loss, row_rank};
 }
 
+// ------------------------------------------------------------------ kNN evaluation (knn.hip)
+// Everything outside the kernels' domain raises here, before a launch.
+std::tuple<at::Tensor, at::Tensor> knn_topk(const at::Tensor& q, const at::Tensor& bank, int64_t k, int64_t splits) {
+  expect(q, at::kBFloat16, "q");
+  expect(bank, at::kBFloat16, "bank");
+  TORCH_CHECK(q.dim() == 2 && bank.dim() == 2 && q.size(1) == bank.size(1), "knn_topk: q [Q, D] and bank [N, D]");
+  TORCH_CHECK(q.get_device() == bank.get_device(), "knn_topk: q and bank on different devices");
+  const int64_t Q = q.size(0), N = bank.size(0), D = q.size(1);
+  TORCH_CHECK(D % 16 == 0 && D >= 16 && D <= 4096, "knn_topk: D = ", D, " must be a multiple of 16 in 16 .. 4096");
+  TORCH_CHECK(k >= 1 && k <= 256 && k <= N, "knn_topk: k = ", k, " must be in 1 .. min(256, N = ", N, ")");
+  TORCH_CHECK(Q <= INT32_MAX && N <= INT32_MAX, "knn_topk: too many rows");
+  const int max_splits = dl_knn_max_splits((int)N, (int)k);
+  TORCH_CHECK(splits >= 0 && splits <= max_splits, "knn_topk: splits = ", splits, " must be 0 (automatic) or 1 .. ",
+              max_splits, " for N = ", N, ", k = ", k);
+  auto vals = at::empty({Q, k}, q.options().dtype(at::kFloat));
+  auto idx = at::empty({Q, k}, q.options().dtype(at::kInt));
+  if (Q == 0) return {vals, idx};
+  int cus = 0;
+  if (splits == 0)
+    TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, q.get_device()) == hipSuccess,
+                "knn_topk: cannot read the device's CU count");
+  const int S = splits > 0 ? (int)splits : dl_knn_splits((int)Q, (int)N, (int)k, cus);
+  auto lists = at::empty({dl_knn_list_entries((int)Q, (int)k, S)}, q.options().dtype(at::kLong));
+  at::Tensor part;
+  if (S > 1) part = at::empty({Q * S * k}, q.options().dtype(at::kLong));
+  check(dl_knn_topk(cbf(q), cbf(bank), (int)Q, (int)N, (int)D, (int)k, S,
+                    reinterpret_cast<unsigned long long*>(lists.data_ptr<int64_t>()),
+                    S > 1 ? reinterpret_cast<unsigned long long*>(part.data_ptr<int64_t>()) : nullptr, f32(vals),
+                    idx.data_ptr<int>(), cur_stream(q)),
+        "knn_topk");
+  return {vals, idx};
+}
+
+std::tuple<at::Tensor, at::Tensor> knn_vote(const at::Tensor& vals, const at::Tensor& idx, const at::Tensor& bank_labels,
+                                            const at::Tensor& targets, int64_t num_classes, double sigma) {
+  expect(vals, at::kFloat, "vals");
+  expect(idx, at::kInt, "idx");
+  expect(bank_labels, at::kInt, "bank_labels");
+  expect(targets, at::kLong, "targets");
+  TORCH_CHECK(vals.dim() == 2 && idx.sizes() == vals.sizes(), "knn_vote: vals and idx must both be [Q, k]");
+  const int64_t Q = vals.size(0), k = vals.size(1), N = bank_labels.numel();
+  TORCH_CHECK(k >= 1 && k <= 256, "knn_vote: k = ", k, " must be in 1 .. 256");
+  TORCH_CHECK(targets.numel() == Q, "knn_vote: targets has ", targets.numel(), " elements for ", Q, " rows");
+  TORCH_CHECK(N >= 1 && N <= INT32_MAX && Q <= INT32_MAX, "knn_vote: bank_labels must hold 1 .. 2^31 - 1 labels");
+  TORCH_CHECK(num_classes >= 1 && num_classes <= 8192, "knn_vote: num_classes = ", num_classes, " must be in 1 .. 8192");
+  TORCH_CHECK(sigma > 0, "knn_vote: sigma must be positive");
+  auto pred = at::empty({Q}, vals.options().dtype(at::kInt));
+  auto rank = at::empty({Q}, vals.options().dtype(at::kInt));
+  check(dl_knn_vote(f32(vals), idx.data_ptr<int>(), bank_labels.data_ptr<int>(), targets.data_ptr<long>(),
+                    pred.data_ptr<int>(), rank.data_ptr<int>(), (int)Q, (int)k, (int)N, (int)num_classes, (float)sigma,
+                    cur_stream(vals)),
+        "knn_vote");
+  return {pred, rank};
+}
+
 // ------------------------------------------------------------------ attention
 inline const int* kvinfo_ptr(const c10::optional<at::Tensor>& kvinfo, int64_t B) {
   if (!kvinfo.has_value()) return nullptr;
@@ -1739,6 +1794,8 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("embed_bwd", &embed_bwd);
   m.impl("xent_fwd_bwd", &xent_fwd_bwd);
   m.impl("xent_eval", &xent_eval);
+  m.impl("knn_topk", &knn_topk);
+  m.impl("knn_vote", &knn_vote);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
   m.impl("attn_varlen_fwd", &attn_varlen_fwd);

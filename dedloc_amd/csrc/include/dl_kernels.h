@@ -86,6 +86,19 @@ int dl_xent_fwd_bwd(const bf16_t* logits, const long* labels, bf16_t* dlogits, f
 int dl_xent_eval(const bf16_t* logits, const long* labels, float* row_loss, int* row_rank, int M, int V, long ld,
                  int ignore_index, hipStream_t st);
 
+// knn.hip  (kNN evaluation: fused similarity + top-k over bank slices, slice merge, weighted vote)
+// q [Q, D], bank [N, D] bf16 rows (16-byte aligned, D % 16 == 0, 16 <= D <= 4096), 1 <= k <= min(256, N),
+// 1 <= splits <= dl_knn_max_splits.  lists: dl_knn_list_entries(Q, k, splits) 64-bit words of
+// scratch; part: Q * splits * k words (splits > 1).  vals [Q, k] fp32, idx [Q, k] int32.
+int dl_knn_max_splits(int N, int k);
+int dl_knn_splits(int Q, int N, int k, int cus);  // the automatic number of slices
+long dl_knn_list_entries(int Q, int k, int splits);
+int dl_knn_topk(const bf16_t* q, const bf16_t* bank, int Q, int N, int D, int k, int splits, unsigned long long* lists,
+                unsigned long long* part, float* vals, int* idx, hipStream_t st);
+// labels [N] int32, targets [Q] int64, 1 <= C <= 8192, k <= 256: pred [Q], rank [Q] int32
+int dl_knn_vote(const float* vals, const int* idx, const int* labels, const long* targets, int* pred, int* rank, int Q,
+                int k, int N, int C, float sigma, hipStream_t st);
+
 // BatchNorm+ReLU backward preparation fused into a data-gradient GEMM epilogue (gemm8
 // DL_EPI_BNBWD, gemm_small): the GEMM's output is dY of the BN's output; the epilogue masks it by the ReLU
 // (Y > 0, or the forward's pre-activation X*gamma*rstd + beta - mean*gamma*rstd > 0 when Y is null),

@@ -11,7 +11,7 @@
 //                 (h, w) — a gather, so no atomics and a deterministic result
 //   avgpool_fwd : y[n,c] = mean_{h,w} x[n,h,w,c]   (bf16 out; one block per (n, 256-channel chunk))
 //   avgpool_bwd : dx[n,h,w,c] = dy[n,c] / (H W)
-//   l2norm_fwd  : y = x / max(||x||, eps) per row (rows of D <= 1024 bf16), inverse norm kept (fp32)
+//   l2norm_fwd  : y = x / max(||x||, eps) per row (rows of D <= 4096 bf16), inverse norm kept (fp32)
 //   l2norm_bwd  : dx = (dy - y <y, dy>) / max(||x||, eps)
 #include <algorithm>
 
@@ -160,16 +160,18 @@ __global__ __launch_bounds__(256) void avgpool_bwd_kernel(const bf16_t* __restri
   }
 }
 
-// one wave per row, D <= 1024 (16 values per lane)
+// one wave per row, D <= 64 NV (NV values per lane: 16 for the 128-d embeddings, 64 up to D = 4096,
+// the kNN evaluation's 2048-d trunk features)
+template <int NV>
 __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const bf16_t* __restrict__ x, bf16_t* __restrict__ y,
                                                          float* __restrict__ rinv, int rows, int D, float eps) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  float v[16];
+  float v[NV];
   float ss = 0.f;
 #pragma unroll
-  for (int j = 0; j < 16; ++j) {
+  for (int j = 0; j < NV; ++j) {
     const int d = lane + 64 * j;
     v[j] = d < D ? bf2f(x[(long)row * D + d]) : 0.f;
     ss += v[j] * v[j];
@@ -177,7 +179,7 @@ __global__ __launch_bounds__(256) void l2norm_fwd_kernel(const bf16_t* __restric
   ss = wave_sum(ss);
   const float r = 1.f / fmaxf(sqrtf(ss), eps);
 #pragma unroll
-  for (int j = 0; j < 16; ++j) {
+  for (int j = 0; j < NV; ++j) {
     const int d = lane + 64 * j;
     if (d < D) y[(long)row * D + d] = f2bf(v[j] * r);
   }
@@ -238,8 +240,9 @@ int dl_avgpool_bwd(const bf16_t* dy, bf16_t* dx, int N, int HW, int C, hipStream
 }
 
 int dl_l2norm_fwd(const bf16_t* x, bf16_t* y, float* rinv, int rows, int D, float eps, hipStream_t st) {
-  if (D > 1024 || rows <= 0) return -1;
-  l2norm_fwd_kernel<<<(rows + 3) / 4, 256, 0, st>>>(x, y, rinv, rows, D, eps);
+  if (D > 4096 || rows <= 0) return -1;
+  if (D <= 1024) l2norm_fwd_kernel<16><<<(rows + 3) / 4, 256, 0, st>>>(x, y, rinv, rows, D, eps);
+  else l2norm_fwd_kernel<64><<<(rows + 3) / 4, 256, 0, st>>>(x, y, rinv, rows, D, eps);
   return 0;
 }
 

@@ -205,6 +205,26 @@ class MultiCropAugment:
         flip, tail = self._draw_flip_color_blur(nb, gen)
         return torch.cat([torch.stack([src.double(), j, i, w * flip, h], 1), tail], 1).float()
 
+    @staticmethod
+    def center_params(src: torch.Tensor, H: torch.Tensor, W: torch.Tensor, size: int, resize: int) -> torch.Tensor:
+        """The evaluation transform ``Resize(resize)`` + ``CenterCrop(size)`` as a [n, 20] table for
+        ``dedloc::multicrop_ragged``: the centred square box of side
+        max(1, round(min(H, W) * size / resize)) (at most the image's shorter side), which the
+        sampler resizes to ``size`` with the same area-aware bilinear filter; no mirror, and the
+        colour columns at identity (brightness, contrast, saturation 1, apply 0, grey 0, identity
+        hue matrix, sigma 0).  One difference from resizing first and cropping after: the filter's
+        taps at the box edge do not see the pixels outside the box."""
+        Hd, Wd = H.double(), W.double()
+        short = torch.minimum(Hd, Wd)
+        side = torch.floor(short * size / resize + 0.5).clamp(min=1.0)
+        side = torch.minimum(side, short)
+        j, i = torch.floor((Wd - side) / 2), torch.floor((Hd - side) / 2)
+        p = torch.zeros(src.shape[0], 20, dtype=torch.float64)
+        p[:, 0], p[:, 1], p[:, 2], p[:, 3], p[:, 4] = src.double(), j, i, side, side
+        p[:, 5:8] = 1.0
+        p[:, 10], p[:, 14], p[:, 18] = 1.0, 1.0, 1.0
+        return p.float()
+
     @torch.no_grad()
     def ragged(self, data: torch.Tensor, meta: torch.Tensor, H: torch.Tensor, W: torch.Tensor, gen: torch.Generator,
                out_dtype=torch.bfloat16) -> List[torch.Tensor]:

@@ -24,6 +24,7 @@ from __future__ import annotations
 
 from typing import List, Sequence
 
+import contextlib
 import os
 
 import torch
@@ -857,23 +858,41 @@ class SwAVModel(nn.Module):
         one trunk pass per crop computes — every other trunk op is per-sample.  Without it, BN
         statistics span the whole resolution group (original SwAV's idx_crops grouping).
         """
+        with self._bound_weights(crops[0].device):
+            return self._forward(crops)
+
+    @contextlib.contextmanager
+    def _bound_weights(self, device):
+        """For the duration of one forward: every conv / linear layer reads its bf16 weight from the
+        flat buffer's mirror (refreshed once here) and the convs share it across the trunk passes."""
         convs = [m for m in self.trunk.modules() if isinstance(m, ConvNHWC)]
         token = object()  # this iteration's weights: the data-gradient weight cache key (_dgrad_weights)
         for m in convs:
             m._wb_cache, m._wb_share, m._wd_token = None, True, token
         flat = self._flat
-        if flat is not None and flat.bf16.device == crops[0].device:
+        if flat is not None and flat.bf16.device == device:
             flat.refresh_bf16()
             for m, n in self._wb_names:
                 m._wb_cache = flat.w(n)
         try:
-            return self._forward(crops)
+            yield
         finally:
             for m in convs:
                 m._wb_cache, m._wb_share = None, False
             for m in self.heads.modules():
                 if isinstance(m, HeadLinear):
                     m._wb_cache = None
+
+    def features(self, x: torch.Tensor, feature: str = "trunk") -> torch.Tensor:
+        """Frozen features of one batch of images for evaluation: ``trunk`` the pooled 2048-d trunk
+        output, ``head`` the 128-d projection (before its normalisation); one plain trunk pass, no
+        prototypes.  Meant for ``eval()`` mode under ``no_grad`` (training/swav_eval.py)."""
+        if feature not in ("trunk", "head"):
+            raise ValueError(f"feature must be 'trunk' or 'head', got {feature!r}")
+        with self._bound_weights(x.device):
+            self.set_bn_stat_groups(1)
+            f = self.trunk(x)
+            return f if feature == "trunk" else self.heads[0].projection_head(f)
 
     def _forward(self, crops):
         groups, i = [], 0

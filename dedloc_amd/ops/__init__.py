@@ -329,9 +329,35 @@ def eval_cross_entropy(logits, labels, ignore_index=-100, topk=(1, 5)):
     return out
 
 
+@torch.no_grad()
+def knn_topk(q, bank, k, splits=0):
+    """The ``k`` nearest bank rows of every query row by dot product (the fused similarity + top-k
+    kernel: no score matrix in memory): ``vals`` [Q, k] fp32 and ``idx`` [Q, k] int32, ordered by
+    (score descending, bank index ascending).  ``q`` [Q, D] and ``bank`` [N, D] are brought to
+    contiguous bf16; ``splits`` = 0 lets the kernel choose its number of bank slices."""
+    return OPS.knn_topk(q.to(torch.bfloat16).contiguous(), bank.to(torch.bfloat16).contiguous(), int(k), int(splits))
+
+
+@torch.no_grad()
+def knn_classify(q, bank, bank_labels, targets, num_classes, k=200, sigma=0.1, splits=0):
+    """Weighted k-nearest-neighbour classification of the rows of ``q`` against a labelled bank
+    (``knn_topk`` + ``knn_vote``, k cut to the bank's size).  Returns device scalars ``count`` (rows
+    whose target is a class id), ``top1`` and ``top5`` (int64: rank 0, rank 0..4; a target no
+    neighbour voted for has rank -1 and is a miss) and the per-row ``pred`` / ``rank`` (int32).
+    Nothing is read back."""
+    k = max(1, min(int(k), bank.shape[0]))
+    vals, idx = knn_topk(q, bank, k, splits)
+    targets = targets.to(torch.int64).reshape(-1).contiguous()
+    pred, rank = OPS.knn_vote(vals, idx, bank_labels.to(torch.int32).contiguous(), targets, int(num_classes),
+                              float(sigma))
+    count = ((targets >= 0) & (targets < int(num_classes))).sum()
+    return {"count": count, "top1": (rank == 0).sum(), "top5": ((rank >= 0) & (rank < 5)).sum(), "pred": pred,
+            "rank": rank}
+
+
 __all__ = [
     "linear", "gelu_new", "tanh", "add_layernorm", "attention", "embed_layernorm", "cross_entropy",
-    "eval_cross_entropy", "OPS",
+    "eval_cross_entropy", "knn_topk", "knn_classify", "OPS",
     "load_native", "native_loaded",
 ]
 

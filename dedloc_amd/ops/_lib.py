@@ -43,6 +43,9 @@ _SCHEMAS = [
     "embed_bwd(Tensor ds, Tensor ids, Tensor? tt, Tensor(a!) dwemb, Tensor(b!) dpemb, Tensor(c!) dtemb, int S) -> ()",
     "xent_fwd_bwd(Tensor logits, Tensor labels, bool inplace, int ignore_index) -> (Tensor, Tensor)",
     "xent_eval(Tensor logits, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
+    "knn_topk(Tensor q, Tensor bank, int k, int splits=0) -> (Tensor, Tensor)",
+    "knn_vote(Tensor vals, Tensor idx, Tensor bank_labels, Tensor targets, int num_classes, float sigma) "
+    "-> (Tensor, Tensor)",
     "attn_fwd(Tensor qkv, Tensor? mbias, int H, int S, float scale, Tensor? kvinfo=None) -> (Tensor, Tensor)",
     "attn_bwd(Tensor qkv, Tensor? mbias, Tensor out, Tensor dout, Tensor lse, int H, int S, float scale, "
     "Tensor? kvinfo=None, Tensor(a!)? dbias=None) -> Tensor",
@@ -519,6 +522,68 @@ def _xent_eval_cpu(logits, labels, ignore_index):
     loss = torch.where(valid, loss, torch.where(lab == ignore_index, 0.0, float("nan")).float())
     rank = torch.where(valid, rank, torch.full_like(rank, -1))
     return loss.float(), rank.to(torch.int32)
+
+
+@_impl("knn_topk")
+def _knn_topk_cpu(q, bank, k, splits=0):
+    """Per query row the k largest s[i, j] = sum_d q[i, d] bank[j, d] (bf16 values, fp32 sum) under the
+    order (score descending, bank index ascending): vals [Q, k] fp32, idx [Q, k] int32.  Any D; ``splits``
+    is the GPU kernel's schedule and does not change the result."""
+    if q.dim() != 2 or bank.dim() != 2 or q.shape[1] != bank.shape[1]:
+        raise RuntimeError("knn_topk: q [Q, D] and bank [N, D]")
+    if q.dtype != torch.bfloat16 or bank.dtype != torch.bfloat16 or not (q.is_contiguous() and bank.is_contiguous()):
+        raise RuntimeError("knn_topk: q and bank must be contiguous bf16 tensors")
+    Q, N = q.shape[0], bank.shape[0]
+    if not 1 <= k <= min(256, N):
+        raise RuntimeError(f"knn_topk: k = {k} must be in 1 .. min(256, N = {N})")
+    if splits < 0:
+        raise RuntimeError(f"knn_topk: splits = {splits} must be 0 (automatic) or positive")
+    vals = torch.empty(Q, k, dtype=torch.float32)
+    idx = torch.empty(Q, k, dtype=torch.int32)
+    bf = bank.float().t()
+    for r0 in range(0, Q, 512):
+        s = q[r0:r0 + 512].float() @ bf
+        # a stable descending sort keeps equal scores in index order
+        v, i = torch.sort(s + 0.0, dim=1, descending=True, stable=True)
+        vals[r0:r0 + 512], idx[r0:r0 + 512] = v[:, :k], i[:, :k].to(torch.int32)
+    return vals, idx
+
+
+@_impl("knn_vote")
+def _knn_vote_cpu(vals, idx, bank_labels, targets, num_classes, sigma):
+    """Weighted vote over each row's neighbours (weight exp((vals[., j] - vals[., 0]) / sigma), class
+    sums in fp32 in neighbour order): pred [Q] (lower class id on ties) and the target's rank [Q]
+    (-1: target outside [0, num_classes) or without a vote), both int32."""
+    if vals.dim() != 2 or idx.shape != vals.shape or vals.shape[1] < 1:
+        raise RuntimeError("knn_vote: vals and idx must both be [Q, k] with k >= 1")
+    if not 1 <= num_classes <= 8192 or not sigma > 0:
+        raise RuntimeError("knn_vote: num_classes must be in 1 .. 8192 and sigma positive")
+    Q, k = vals.shape
+    C, N = int(num_classes), bank_labels.numel()
+    if targets.numel() != Q or N < 1:
+        raise RuntimeError("knn_vote: one target per row and at least one bank label")
+    i = idx.long()
+    inside = (i >= 0) & (i < N)
+    cls = bank_labels.long()[i.clamp(0, N - 1)]
+    votes = inside & (cls >= 0) & (cls < C)
+    w = torch.exp((vals.float() - vals[:, :1].float()) / torch.tensor(sigma, dtype=torch.float32))
+    sums = torch.zeros(Q, C, dtype=torch.float32)
+    voted = torch.zeros(Q, C, dtype=torch.bool)
+    rows = torch.arange(Q)
+    for j in range(k):  # one class per row and step: the sum's order is the neighbour order
+        r, c = rows[votes[:, j]], cls[votes[:, j], j]
+        sums[r, c] += w[votes[:, j], j]
+        voted[r, c] = True
+    col = torch.arange(C)[None, :]
+    best = sums.max(1, keepdim=True).values
+    pred = torch.where(sums == best, col, C).min(1).values
+    t = targets.reshape(-1)
+    valid = (t >= 0) & (t < C)
+    safe = torch.where(valid, t, torch.zeros_like(t))
+    pt = sums.gather(1, safe[:, None])
+    rank = ((sums > pt) | ((sums == pt) & (col < safe[:, None]))).sum(1)
+    valid = valid & voted.gather(1, safe[:, None]).squeeze(1)
+    return pred.to(torch.int32), torch.where(valid, rank, torch.full_like(rank, -1)).to(torch.int32)
 
 
 def _attn_probs(qkv, mbias, H, S, scale):

@@ -77,6 +77,9 @@ class SwavPeer:
             raise ValueError(f"DATA.TRAIN.DATA_SOURCES={sources!r}: the sources are 'synthetic' and 'disk_folder'")
         if source == "disk_folder" and not dcfg.get("DATA_PATHS"):
             raise ValueError("DATA.TRAIN.DATA_SOURCES=[disk_folder] needs DATA.TRAIN.DATA_PATHS=[directory, ...]")
+        self.knn = self._knn_settings(cfg, source)  # None: no evaluation (the default)
+        if self.knn is not None and impl != "dedloc":
+            raise ValueError("NEAREST_NEIGHBOR.EVAL_FREQUENCY: kNN evaluation runs on the dedloc model only")
         if impl == "eager":
             from .swav_eager import EagerSwAVModel
 
@@ -191,6 +194,38 @@ class SwavPeer:
         self.mini_steps = 0
         self.last_reported_step = -1
         self.metrics_log = []
+
+    # ------------------------------------------------------------------ kNN evaluation
+    @staticmethod
+    def _knn_settings(cfg, source):
+        """NEAREST_NEIGHBOR (the reference's SIGMA / TOPK spelling) when EVAL_FREQUENCY > 0, with the
+        labelled bank and query datasets opened and their fixed subsets drawn: the same images on
+        every peer and at every evaluation.  Raises before anything is started."""
+        from .swav_eval import build_knn_sets
+
+        nn_cfg = cfg.get("NEAREST_NEIGHBOR") or {}
+        freq = int(nn_cfg.get("EVAL_FREQUENCY", 0) or 0)
+        if freq <= 0:
+            return None
+        if source != "disk_folder":
+            raise ValueError("NEAREST_NEIGHBOR.EVAL_FREQUENCY needs labelled images: DATA.TRAIN.DATA_SOURCES="
+                             "[disk_folder] (the synthetic source has no classes)")
+        return dict(build_knn_sets(cfg), frequency=freq)
+
+    def evaluate(self):
+        """One kNN evaluation (outside any captured graph); appends its record to METRICS_FILE."""
+        from .swav_eval import knn_evaluate_sets
+
+        rec = dict(knn_evaluate_sets(self.model, self.knn, self.device), eval=True,
+                   step=int(self.collab_opt.local_step), iteration=self.iteration, time=time.time())
+        self.metrics_log.append(rec)
+        if self.cfg.get("METRICS_FILE"):
+            with open(self.cfg.METRICS_FILE, "a") as f:
+                f.write(json.dumps(rec) + "\n")
+        logger.info(f"collaborative step {rec['step']}: kNN top-1 {rec['knn_top1']:.4f} top-5 {rec['knn_top5']:.4f} "
+                    f"({rec['knn_samples']} queries, bank {rec['knn_bank']}, k {rec['knn_k']})")
+        self._last_eval_step = rec["step"]
+        return rec
 
     # ------------------------------------------------------------------ one local iteration
     # ------------------------------------------------------------------ HIP-graph capture
@@ -341,6 +376,8 @@ class SwavPeer:
                     f"lr {self.opt.param_groups[0]['lr']:.4g}")
         self._loss_sum.zero_()
         self.mini_steps = 0
+        if self.knn is not None and co.local_step > 0 and co.local_step % self.knn["frequency"] == 0:
+            self.evaluate()
 
     def _check_nan_async(self):
         """Every LOG_FREQUENCY iterations: queue a device-to-pinned-host copy of the running loss's
@@ -433,6 +470,8 @@ class SwavPeer:
                 break
             if max_seconds is not None and time.time() - t0 > max_seconds:
                 break
+        if self.knn is not None and getattr(self, "_last_eval_step", None) != int(self.collab_opt.local_step):
+            self.evaluate()  # the end of train(), unless this global step was just evaluated
 
     def shutdown(self):
         if hasattr(self.data, "close"):  # disk_folder: the decode threads
