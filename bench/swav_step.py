@@ -34,12 +34,16 @@ def main():
     ap.add_argument("--model_attr", action="append", default=[],
                     help="NAME=INT: set a SwAVModel class attribute for an A/B (e.g. dgrad_weights_stream=0)")
     ap.add_argument("--no_prefetch", action="store_true", help="generate each batch in line (no side-stream prefetch)")
+    ap.add_argument("--checkpoint", action="store_true",
+                    help="activation checkpointing: layer1-layer3 replayed per stage (concurrent passes and graphs are then off)")
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     ov = [f"config.DATA.TRAIN.BATCHSIZE_PER_REPLICA={args.batch}", f"config.OPTIMIZER.batch_size_for_tracking={args.batch}",
           "config.OPTIMIZER.target_batch_size=100000000", f"config.MODEL.SINGLE_PASS_EVERY_CROP={not args.grouped}",
           f"config.LOSS.swav_loss.queue.start_iter={0 if args.queue else 10**9}", "config.CHECKPOINT.DIR=/tmp/swav_bench", f"config.MODEL.CUDA_GRAPH={args.graph}",
           f"config.MODEL.CONCURRENT_PASSES={not args.sequential}", f"config.DATA.TRAIN.PREFETCH={not args.no_prefetch}"]
+    if args.checkpoint:
+        ov.append("config.MODEL.ACTIVATION_CHECKPOINTING.USE_ACTIVATION_CHECKPOINTING=true")
     ov += args.cfg
     if args.splits:
         ov.append(f"config.MODEL.CONCURRENT_SPLITS=[{args.splits}]")
@@ -58,6 +62,7 @@ def main():
             peer.train_step()
             torch.cuda.synchronize()
             print(f"warmup {i}: {time.perf_counter() - t0:.2f}s", file=sys.stderr, flush=True)
+        torch.cuda.reset_peak_memory_stats()
         t = time.perf_counter()
         for _ in range(args.iters):
             peer.train_step()
@@ -76,7 +81,8 @@ def main():
         print(json.dumps({"metric": "swav_rn50_local_samples_per_sec_per_gpu", "value": args.batch / dt,
                           "ms_per_iter": dt * 1e3, "data_ms": data_ms, "larc_sgd_step_ms": opt_ms,
                           "batch": args.batch, "crops": "2x224+6x96", "grouped": args.grouped, "queue": args.queue, "hip_graph": args.graph,
-                          "concurrent_passes": not args.sequential, "splits": args.splits, "prefetch": not args.no_prefetch,
+                          "concurrent_passes": not args.sequential and not args.checkpoint, "splits": args.splits, "prefetch": not args.no_prefetch,
+                          "checkpoint": args.checkpoint, "max_memory_allocated": torch.cuda.max_memory_allocated(),
                           "peak_mem_gb": torch.cuda.max_memory_allocated() / 2**30}))
     finally:
         peer.shutdown()

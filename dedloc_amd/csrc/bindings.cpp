@@ -1132,6 +1132,31 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_fwd(const at::Tensor& x, const
   return {y, stats.narrow(0, 2 * G * C, G * C).view({G, C}), stats.narrow(0, 3 * G * C, G * C).view({G, C})};
 }
 
+at::Tensor bn_apply(const at::Tensor& x, const c10::optional<at::Tensor>& res, const at::Tensor& gamma,
+                    const at::Tensor& beta, const at::Tensor& mean, const at::Tensor& rstd, bool relu,
+                    int64_t groups) {
+  expect_nhwc(x, "x");
+  if (res.has_value()) {
+    expect_nhwc(*res, "res");
+    TORCH_CHECK(res->sizes() == x.sizes(), "bn_apply: res must have x's shape");
+  }
+  expect(gamma, at::kFloat, "gamma");
+  expect(beta, at::kFloat, "beta");
+  expect(mean, at::kFloat, "mean");
+  expect(rstd, at::kFloat, "rstd");
+  const int64_t C = x.size(1), G = groups;
+  TORCH_CHECK(G >= 1 && x.size(0) % G == 0, "batch must split into `groups` equal statistics groups");
+  TORCH_CHECK(gamma.numel() == C && beta.numel() == C, "bn_apply: gamma / beta must hold C floats");
+  TORCH_CHECK(mean.numel() == G * C && rstd.numel() == G * C && mean.is_contiguous() && rstd.is_contiguous(),
+              "bn_apply: mean / rstd must be contiguous [groups, C] (what bn_fwd returned)");
+  const int64_t R = x.numel() / C / G;
+  auto y = at::empty_like(x);
+  check(dl_bn_apply(cbf(x), res.has_value() ? cbf(*res) : nullptr, bf(y), f32(gamma), f32(beta), f32(mean), f32(rstd),
+                    R, (int)C, (int)G, relu, cur_stream(x)),
+        "bn_apply (channels must be 64..2048, a power-of-two multiple of 8)");
+  return y;
+}
+
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> bn_bwd(const at::Tensor& dy, const at::Tensor& y,
                                                                   const at::Tensor& x, const at::Tensor& mean,
                                                                   const at::Tensor& rstd, const at::Tensor& gamma,
@@ -1756,6 +1781,7 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("conv2d_dgrad", &conv2d_dgrad);
   m.impl("conv2d_wgrad", &conv2d_wgrad);
   m.impl("bn_fwd", &bn_fwd);
+  m.impl("bn_apply", &bn_apply);
   m.impl("bn_bwd", &bn_bwd);
   m.impl("sinkhorn", &sinkhorn);
   m.impl("swav_ce", &swav_ce);

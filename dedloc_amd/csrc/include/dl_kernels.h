@@ -174,6 +174,10 @@ int dl_multicrop_ragged(const unsigned char* bytes, long nbytes, const long* met
 int dl_bn_fwd(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* gamma, const float* beta, float* sums,
               float* mean, float* rstd, float* run_mean, float* run_var, long R, int C, int G, float eps,
               float momentum, int relu, hipStream_t st, int sums_zeroed = 0, int stats_ready = 0);
+// y = act(BN(x) [+ res]) from the mean / rstd [G, C] that a dl_bn_fwd call returned: the streaming
+// pass alone (bit-equal to that call's y); writes neither statistics nor running statistics
+int dl_bn_apply(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* gamma, const float* beta,
+                const float* mean, const float* rstd, long R, int C, int G, int relu, hipStream_t st);
 // BatchNorm forward statistics alone (sums [G][2C] += per-group channel sums / sums of squares of
 // x [G*R, C]); dl_bn_fwd with stats_ready = 1 then skips its own statistics pass
 int dl_bn_stats(const bf16_t* x, float* sums, long R, int C, int G, hipStream_t st);

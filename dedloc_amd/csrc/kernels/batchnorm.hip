@@ -83,7 +83,12 @@ __global__ __launch_bounds__(kThreads) void bn_stats_kernel(const bf16_t* __rest
 
 // ---------------------------------------------------------------------------------- forward apply
 // HR / RL: residual input / ReLU, template flags (as run-time flags they were per-element selects)
-template <int BN_U, bool HR, bool RL>
+// SV: the statistics source, template flag — false: the sums (mean / rstd are derived, written by
+// block 0 and folded into the running statistics); true: mean_out / rstd_out hold a previous call's
+// saved [G, C] mean / rstd and are only read (dl_bn_apply: sums and the running statistics are not
+// touched).  Scale / shift are the same two expressions either way and the streaming loops are
+// shared, so y from saved statistics is bit-equal to the y of the call that saved them.
+template <int BN_U, bool HR, bool RL, bool SV = false>
 __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const bf16_t* __restrict__ x,
                                                             const bf16_t* __restrict__ res, bf16_t* __restrict__ y,
                                                             const float* __restrict__ sums,
@@ -96,18 +101,24 @@ __global__ __launch_bounds__(kThreads) void bn_apply_kernel(const bf16_t* __rest
   const int grp = blockIdx.y, G = gridDim.y;
   const float invR = 1.f / (float)R;
   for (int c = threadIdx.x; c < C; c += kThreads) {
-    const float* sg = sums + (long)grp * 2 * C;
-    const float mean = sg[c] * invR;
-    const float var = fmaxf(sg[C + c] * invR - mean * mean, 0.f);
-    const float rstd = rsqrtf(var + eps);
+    float mean, rstd;
+    if (SV) {
+      mean = mean_out[(long)grp * C + c];
+      rstd = rstd_out[(long)grp * C + c];
+    } else {
+      const float* sg = sums + (long)grp * 2 * C;
+      mean = sg[c] * invR;
+      const float var = fmaxf(sg[C + c] * invR - mean * mean, 0.f);
+      rstd = rsqrtf(var + eps);
+    }
     const float g = gamma[c] * rstd;
     sc[c] = g;
     sh[c] = beta[c] - mean * g;
-    if (blockIdx.x == 0) {
+    if (!SV && blockIdx.x == 0) {
       mean_out[(long)grp * C + c] = mean;
       rstd_out[(long)grp * C + c] = rstd;
     }
-    if (blockIdx.x == 0 && grp == 0 && run_mean != nullptr) {  // G momentum updates, in group order
+    if (!SV && blockIdx.x == 0 && grp == 0 && run_mean != nullptr) {  // G momentum updates, in group order
       float rm = run_mean[c], rv = run_var[c];
       for (int k = 0; k < G; ++k) {
         const float* sk = sums + (long)k * 2 * C;
@@ -457,6 +468,29 @@ int dl_bn_fwd(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* gamma,
     else DL_BN_APPLY(false, false);
   }
 #undef DL_BN_APPLY
+  return 0;
+}
+
+// y = act(BN(x) [+ res]) from the [G, C] mean / rstd a dl_bn_fwd call saved (a checkpointed
+// segment's recompute): one streaming pass — no statistics pass, no memset, no atomics; mean / rstd
+// and the running statistics are not written.  Shape contract and grid as dl_bn_fwd.
+int dl_bn_apply(const bf16_t* x, const bf16_t* res, bf16_t* y, const float* gamma, const float* beta,
+                const float* mean, const float* rstd, long R, int C, int G, int relu, hipStream_t st) {
+  if (!bn_shape_ok(C) || R < 1 || G < 1) return -1;
+  const int na = (apply_blocks(R * (C / 8) * G) + G - 1) / G;
+  float* mp = const_cast<float*>(mean);  // SV = true only reads them
+  float* rp = const_cast<float*>(rstd);
+#define DL_BN_APPLY_SV(HR_, RL_)                                                                          \
+  bn_apply_kernel<2, HR_, RL_, true><<<dim3(na, G), kThreads, 0, st>>>(x, res, y, nullptr, gamma, beta, mp, rp,  \
+                                                                       nullptr, nullptr, R, C, 0.f, 0.f, relu)
+  if (res) {
+    if (relu) DL_BN_APPLY_SV(true, true);
+    else DL_BN_APPLY_SV(true, false);
+  } else {
+    if (relu) DL_BN_APPLY_SV(false, true);
+    else DL_BN_APPLY_SV(false, false);
+  }
+#undef DL_BN_APPLY_SV
   return 0;
 }
 

@@ -1036,6 +1036,11 @@ static long wgrad_splits(const DlConvGeom& g, int tiles) {
   const long M = (long)g.Nimg * g.I * g.J;
   constexpr long target = DL_CONV_WGRAD_TARGET;
   const long ksteps = (M + BK - 1) / BK;
+  // DEDLOC_DETERMINISTIC_BN=1 (parity runs, read at every launch like batchnorm.hip): one split, so
+  // every dW element takes a single fp32 add — three or more split partials added by atomics round
+  // differently from run to run (at small shapes only the stem has that many: 64 k-steps at b=4, 64 px)
+  const char* det = std::getenv("DEDLOC_DETERMINISTIC_BN");
+  if (det != nullptr && det[0] == '1') return 1;
   long splits = std::max(1L, std::min<long>((target + tiles - 1) / tiles, ksteps / 8));
   const long steps_per = (ksteps + splits - 1) / splits;
   return (ksteps + steps_per - 1) / steps_per;

@@ -9,7 +9,9 @@ concatenated before the head).
 MI355X-first choices: channels-last bf16 activations (fp32 master weights live in the flat parameter
 buffer and receive their gradients in place), optional per-resolution batching of the crops
 (``single_pass_every_crop=False``: 2 trunk passes instead of 8), optional activation checkpointing
-per stage (off by default: 288 GB HBM makes the recompute pointless).
+per stage (``_SegmentReplay``: layer1-layer3 recomputed in the backward from the first pass's saved
+BatchNorm statistics, exact under train-mode BN; off by default — one b=64 peer fits 288 GB HBM
+without it — for a larger per-peer batch or several peers per card).
 Parameter names match torchvision/vissl (``trunk.*``, ``heads.0.*``) for checkpoint interchange.
 
 One code path on every device: each op of the model is a ``torch.ops.dedloc`` operator — the HIP
@@ -31,14 +33,15 @@ import torch
 import torch.nn as nn
 
 from .. import ops as _ops  # noqa: F401  (registers torch.ops.dedloc.*)
-from torch.utils.checkpoint import checkpoint
 
 
 def deterministic_bn() -> bool:
     """DEDLOC_DETERMINISTIC_BN=1: bitwise-reproducible BatchNorm statistics for parity runs — every
     statistic is one fixed-order reduction (batchnorm.hip ``bn_deterministic``: one block per
     statistics group) instead of fp32 atomics from many blocks, conv / GEMM epilogues and the
-    BN-backward preparation links (their atomics from many tiles) are bypassed.  Slow; off by default."""
+    BN-backward preparation links (their atomics from many tiles) are bypassed, and the conv weight
+    gradient runs unsplit (conv.hip ``wgrad_splits``: one fp32 add per element instead of several
+    split partials in atomic order).  Slow; off by default."""
     return os.environ.get("DEDLOC_DETERMINISTIC_BN", "") == "1"
 
 
@@ -110,9 +113,16 @@ class _BNAct(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, res, running_mean, running_var, relu, eps, momentum, groups, ws, module,
-                stats_ready=False, link=None, bwd_link=None):
-        y, mean, rstd = torch.ops.dedloc.bn_fwd(x, res, gamma, beta, running_mean, running_var, eps, momentum, relu,
-                                                groups, None if ws is None else ws[0], stats_ready)
+                stats_ready=False, link=None, bwd_link=None, replay=None):
+        if replay is not None and replay.replaying:
+            # a checkpointed segment's recompute: one streaming pass from the first pass's statistics
+            mean, rstd = replay.stats[module]
+            y = torch.ops.dedloc.bn_apply(x, res, gamma, beta, mean, rstd, relu, groups)
+        else:
+            y, mean, rstd = torch.ops.dedloc.bn_fwd(x, res, gamma, beta, running_mean, running_var, eps, momentum,
+                                                    relu, groups, None if ws is None else ws[0], stats_ready)
+            if replay is not None:  # the segment's first pass
+                replay.stats[module] = (mean, rstd)
         ctx.save_for_backward(x, y, mean, rstd, gamma, beta)
         ctx.relu, ctx.has_res, ctx.ws, ctx.module = relu, res is not None, ws, module
         ctx.gslot = getattr(module, "_gslot", None)  # a concurrent second pass's gradient buffers
@@ -148,7 +158,7 @@ class _BNAct(torch.autograd.Function):
         if ctx.link is not None:  # the residual's gradient rides in conv1's data-gradient epilogue
             ctx.link.g, dres = dres, None
         return (dx, dgamma, dbeta, (dres if ctx.has_res else None), None, None, None, None, None, None, None, None,
-                None, None, None)
+                None, None, None, None)
 
 
 class _ConvNHWC(torch.autograd.Function):
@@ -162,11 +172,20 @@ class _ConvNHWC(torch.autograd.Function):
         # of one SwAVModel.forward (one cast per iteration instead of one per resolution group); the
         # model clears the cache at the start and end of every forward, so an optimizer update
         # between iterations can never be missed
-        wb = getattr(module, "_wb_cache", None)
+        # a checkpointed segment (_SegmentReplay): the first pass records a shared bf16 weight (a view
+        # of the flat mirror, unchanged until the next forward refreshes it) and the recompute reads
+        # it back; an unshared cast is not kept alive — the recompute casts the same fp32 weight again
+        rec = module._replay
+        wb = rec.weights.get(module) if rec is not None and rec.replaying else None
         if wb is None:
-            wb = weight.detach().to(torch.bfloat16)
-            if module._wb_share:
-                module._wb_cache = wb
+            wb = getattr(module, "_wb_cache", None)
+            shared = wb is not None or module._wb_share
+            if wb is None:
+                wb = weight.detach().to(torch.bfloat16)
+                if module._wb_share:
+                    module._wb_cache = wb
+            if rec is not None and not rec.replaying and shared:
+                rec.weights[module] = wb
         # the stem (3 input channels): its im2col column matrix is built once here and kept for the
         # weight gradient (the input image needs no gradient, so the matrix replaces it)
         cols = None
@@ -283,6 +302,7 @@ class ConvNHWC(nn.Conv2d):
     _wb_cache = None    # bf16 weight shared across the trunk passes of one model forward
     _wb_share = False   # set by SwAVModel.forward for the duration of that forward
     _gslot = None       # weight-gradient target of a concurrent second trunk pass (SwAVModel)
+    _replay = None      # the _SegmentRecord of the checkpointed segment call in progress
     # False: return the weight gradient through autograd instead of adding it into the bound .grad
     # (HIP-graph capture via make_graphed_callables needs every parameter to receive an autograd grad)
     inplace_wgrad = True
@@ -303,7 +323,9 @@ class ConvNHWC(nn.Conv2d):
             raise NotImplementedError("ConvNHWC: only the ResNet-50 conv forms (no bias, groups 1, square "
                                       "stride/padding) have kernels")
         x = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
-        if bn is not None and self.epilogue_stats and bn.takes_conv_stats() and not deterministic_bn():
+        replaying = self._replay is not None and self._replay.replaying  # the BN applies saved statistics
+        if (bn is not None and self.epilogue_stats and bn.takes_conv_stats() and not deterministic_bn()
+                and not replaying):
             bn.stats_ready = True
             return _ConvNHWC.apply(x, self.weight, self.stride[0], self.padding[0], self, bn.pass_ws[0],
                                    bn.stat_groups, link, bn_link, give)
@@ -325,6 +347,7 @@ class BNAct(nn.BatchNorm2d):
     inplace_grad = True
     _gslot = None        # (dgamma, dbeta) targets of a concurrent second trunk pass (SwAVModel)
     _rs_override = None  # (running_mean, running_var) stand-ins of that pass (deferred update)
+    _replay = None       # the _SegmentRecord of the checkpointed segment call in progress
 
     def __init__(self, num_features, relu: bool = False):
         super().__init__(num_features)
@@ -347,13 +370,20 @@ class BNAct(nn.BatchNorm2d):
         if res is not None:
             _require_nhwc_bf16(res, "BNAct residual")
         G = self.stat_groups
+        rec = self._replay
+        ws, self.pass_ws = self.pass_ws, None
+        if rec is not None and rec.replaying:
+            # the recompute of a checkpointed segment: the first pass counted this call and updated
+            # the running statistics; ws is (None, this call's backward sums)
+            self.stats_ready = False
+            return _BNAct.apply(x, self.weight, self.bias, res, None, None, self.relu,
+                                self.eps, self.momentum, G, ws, self, False, link, bwd_link, rec)
         if not self.count_deferred:
             self.num_batches_tracked.add_(G)
-        ws, self.pass_ws = self.pass_ws, None
         ready, self.stats_ready = self.stats_ready and ws is not None, False
         rm, rv = self._rs_override or (self.running_mean, self.running_var)
         return _BNAct.apply(x, self.weight, self.bias, res, rm, rv, self.relu,
-                            self.eps, self.momentum, G, ws, self, ready, link, bwd_link)
+                            self.eps, self.momentum, G, ws, self, ready, link, bwd_link, rec)
 
 
 def _bn_eval(m, x, res, relu: bool):
@@ -456,6 +486,86 @@ class Bottleneck(nn.Module):
         return y
 
 
+class _SegmentRecord:
+    """What one call of a checkpointed segment leaves for its recompute: every BatchNorm's batch
+    statistics (``stats``: module -> (mean, rstd), [G, C] fp32 as bn_fwd returned them), the shared
+    bf16 weight every conv read (``weights``), the call's statistics groups and the gradient slots in
+    force — per call, because by backward time the modules hold the state of whichever pass ran last."""
+
+    __slots__ = ("stats", "weights", "groups", "gslots", "replaying")
+
+    def __init__(self, mods):
+        self.stats, self.weights, self.replaying = {}, {}, False
+        self.groups = {m: m.stat_groups for m in mods if isinstance(m, BNAct)}
+        self.gslots = {m: m._gslot for m in mods}
+
+
+def _segment_modules(stage):
+    mods = getattr(stage, "_replay_mods", None)
+    if mods is None:
+        mods = stage._replay_mods = [m for m in stage.modules() if isinstance(m, (BNAct, ConvNHWC))]
+    return mods
+
+
+class _SegmentReplay(torch.autograd.Function):
+    """Activation checkpointing of one trunk stage that is exact under train-mode BatchNorm.
+
+    The first pass runs the stage as the plain trunk does (conv-epilogue statistics, running
+    statistics and counters updated once) under ``no_grad``, so nothing of the stage is retained
+    beyond its input, its output and a _SegmentRecord.  The backward runs the stage again from that
+    record — the convs without a statistics epilogue on the recorded bf16 weights, every BatchNorm as
+    one streaming pass from the recorded mean / rstd (``bn_apply``: bit-equal to the first pass's
+    output; counters and running statistics untouched) — with the fused backward live (_BnBwdLink,
+    _GradLink and the shortcut link over one zeroed workspace for the backward sums), and
+    backpropagates the recomputed output.  The weight / BN-parameter gradients land where the plain
+    trunk's do (in place in the bound buffers, or through AccumulateGrad)."""
+
+    @staticmethod
+    def forward(ctx, x, stage):
+        mods = _segment_modules(stage)
+        rec = _SegmentRecord(mods)
+        for m in mods:
+            m._replay = rec
+        try:
+            y = stage(x)  # autograd.Function.forward runs with grad mode off: no links, nothing saved
+        finally:
+            for m in mods:
+                m._replay = None
+        ctx.save_for_backward(x)
+        ctx.stage, ctx.rec = stage, rec
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        stage, rec = ctx.stage, ctx.rec
+        mods = _segment_modules(stage)
+        bns = [m for m in mods if isinstance(m, BNAct)]
+        # one zeroed workspace for the backward sums of the segment's BatchNorms
+        sizes = [2 * rec.groups[m] * m.num_features for m in bns]
+        ws = torch.zeros(sum(sizes), dtype=torch.float32, device=x.device)
+        held = [(m, m._replay, m._gslot) for m in mods]
+        held_bn = [(m, m.stat_groups, m.pass_ws, m.stats_ready) for m in bns]
+        rec.replaying = True
+        try:
+            off = 0
+            for m, n in zip(bns, sizes):
+                m.stat_groups, m.pass_ws, m.stats_ready = rec.groups[m], (None, ws[off:off + n]), False
+                off += n
+            for m in mods:
+                m._replay, m._gslot = rec, rec.gslots[m]
+            xd = x.detach().requires_grad_(True)
+            with torch.enable_grad():
+                y = stage(xd)
+        finally:
+            for m, r, g in held:
+                m._replay, m._gslot = r, g
+            for m, G, pw, sr in held_bn:
+                m.stat_groups, m.pass_ws, m.stats_ready = G, pw, sr
+        torch.autograd.backward(y, dy)
+        return xd.grad, None
+
+
 class ResNet50Trunk(nn.Module):
     pass_workspace = True  # False: per-call BN statistics memsets and counter adds (A/B, tests)
 
@@ -497,7 +607,7 @@ class ResNet50Trunk(nn.Module):
         num_batches_tracked counters (instead of two memsets and one add launch per BatchNorm; each
         is a ~5 us kernel at b=64).  Returns the per-BatchNorm workspace slices for ``forward``'s
         ``prepared`` (None: the per-call path).  ``count=False``: the caller adds the counters."""
-        if not self.pass_workspace or not self.training or self.checkpoint_stages:
+        if not self.pass_workspace or not self.training:
             return None
         bns = self._bn_modules()
         G = bns[0].stat_groups
@@ -528,15 +638,18 @@ class ResNet50Trunk(nn.Module):
 
     def forward(self, x, prepared=None):
         """``prepared``: this pass's BatchNorm workspaces from ``alloc_bn_pass`` (allocated ahead,
-        e.g. on another stream); None allocates them here."""
+        e.g. on another stream); None allocates them here.
+
+        ``checkpoint_stages``: layer1 to layer3 each run as a replayed segment (_SegmentReplay: only
+        the stage's input and output stay alive until its backward).  The stem and layer4 run plain —
+        layer4's recompute would be the first thing the backward does, so it would free nothing.  In
+        ``eval()`` mode, under ``no_grad`` or for an input that takes no gradient every stage runs plain."""
         self._prepare_bn_pass(x, prepared)
         x = self.maxpool(self.bn1(self.conv1(x, self.bn1)))
-        for stage in (self.layer1, self.layer2, self.layer3, self.layer4):
-            if self.checkpoint_stages and self.training and x.requires_grad:
-                x = checkpoint(stage, x, use_reentrant=False)
-            else:
-                x = stage(x)
-        return global_avgpool(x)
+        replay = self.checkpoint_stages and self.training and torch.is_grad_enabled()
+        for stage in (self.layer1, self.layer2, self.layer3):
+            x = _SegmentReplay.apply(x, stage) if replay and x.requires_grad else stage(x)
+        return global_avgpool(self.layer4(x))
 
 
 class _HeadLinearFn(torch.autograd.Function):

@@ -78,6 +78,8 @@ _SCHEMAS = [
     "bn_fwd(Tensor x, Tensor? res, Tensor gamma, Tensor beta, Tensor(a!)? running_mean, Tensor(b!)? running_var, "
     "float eps, float momentum, bool relu, int groups=1, Tensor(c!)? sums=None, bool stats_ready=False) "
     "-> (Tensor, Tensor, Tensor)",
+    "bn_apply(Tensor x, Tensor? res, Tensor gamma, Tensor beta, Tensor mean, Tensor rstd, bool relu, int groups=1) "
+    "-> Tensor",
     "bn_bwd(Tensor dy, Tensor y, Tensor x, Tensor mean, Tensor rstd, Tensor gamma, bool relu, bool want_dres, "
     "Tensor(a!)? sums=None, Tensor(b!)? dgamma_acc=None, Tensor(c!)? dbeta_acc=None, Tensor? beta=None, "
     "bool stats_ready=False) -> (Tensor, Tensor, Tensor, Tensor)",
@@ -896,6 +898,21 @@ def _bn_fwd_cpu(x, res, gamma, beta, running_mean, running_var, eps, momentum, r
             running_mean.mul_(1 - momentum).add_(mean[k], alpha=momentum)
             running_var.mul_(1 - momentum).add_(var[k] * (R / max(R - 1, 1)), alpha=momentum)
     return y.to(x.dtype).contiguous(memory_format=torch.channels_last), mean, rstd
+
+
+@_impl("bn_apply")
+def _bn_apply_cpu(x, res, gamma, beta, mean, rstd, relu, groups=1):
+    # bn_fwd's output expression over the given [G, C] statistics (equal to its y for its own mean / rstd)
+    G = groups
+    xf = x.float().reshape(G, x.shape[0] // G, *x.shape[1:])
+    mean, rstd = mean.reshape(G, -1), rstd.reshape(G, -1)
+    y = (xf - mean[:, None, :, None, None]) * (rstd * gamma)[:, None, :, None, None] + beta.view(1, 1, -1, 1, 1)
+    y = y.reshape(x.shape)
+    if res is not None:
+        y = y + res.float()
+    if relu:
+        y = y.clamp_min(0)
+    return y.to(x.dtype).contiguous(memory_format=torch.channels_last)
 
 
 @_impl("conv2d_fwd")

@@ -185,6 +185,13 @@ class SwavPeer:
         self.frozen = [(name, int(iters)) for name, iters in (mcfg.get("TEMP_FROZEN_PARAMS_ITER_MAP") or [])]
         self.use_graph = bool(mcfg.get("CUDA_GRAPH", False)) and self.device.type == "cuda" and \
             not bool(mcfg.ACTIVATION_CHECKPOINTING.USE_ACTIVATION_CHECKPOINTING) and impl == "dedloc"
+        if bool(mcfg.ACTIVATION_CHECKPOINTING.USE_ACTIVATION_CHECKPOINTING) and impl == "dedloc":
+            # checkpointing buys memory; concurrent passes multiply the live activations and a captured
+            # graph pins them, so both are refused (SwAVModel._concurrent_ok, use_graph above)
+            logger.info("activation checkpointing is on (layer1-layer3 replayed per stage): concurrent trunk "
+                        "passes and HIP-graph capture are off for this peer (MODEL.CONCURRENT_PASSES="
+                        f"{bool(mcfg.get('CONCURRENT_PASSES', True))}, MODEL.CUDA_GRAPH="
+                        f"{bool(mcfg.get('CUDA_GRAPH', False))} are ignored)")
         self.graph_warmup = int(mcfg.get("CUDA_GRAPH_WARMUP", 3))  # eager iterations before the capture
         self._graphed = None
         self.iteration = 0
