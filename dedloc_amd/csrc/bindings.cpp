@@ -10,6 +10,7 @@
 
 #include <atomic>
 #include <cstring>
+#include <map>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -1374,8 +1375,15 @@ inline DlConvGeom geom(const bf16_t* img, int64_t N, int64_t H, int64_t W, int64
 // otherwise one statistics pass runs after the conv)
 // cols (optional): the stem's column matrix from im2col_stem (computed once per pass and kept for the
 // weight gradient instead of being rebuilt there)
+// af (optional, excludes stats): the inference epilogue of conv2d_bn_act
+struct ConvAffine {
+  const float* scale;
+  const float* shift;
+  const bf16_t* res;
+  bool relu;
+};
 at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t stride, int64_t pad, float* stats,
-                           int64_t groups, const c10::optional<at::Tensor>& cols);
+                           int64_t groups, const c10::optional<at::Tensor>& cols, const ConvAffine* af = nullptr);
 
 at::Tensor conv2d_fwd(const at::Tensor& x, const at::Tensor& w, int64_t stride, int64_t pad,
                       const c10::optional<at::Tensor>& cols) {
@@ -1407,8 +1415,32 @@ inline at::Tensor stem_cols_checked(const c10::optional<at::Tensor>& cols, const
   return *cols;
 }
 
+// fp32 zeros / ones [2, C] per device: the mean / rstd with which dl_bn_apply computes
+// fmaf(x, gamma, beta) exactly (sc = gamma * 1, sh = beta - 0 * sc)
+at::Tensor affine_identity_stats(const at::Device& dev, int64_t C) {
+  static std::mutex mu;
+  static std::map<std::pair<int, int64_t>, at::Tensor> cache;
+  std::lock_guard<std::mutex> lock(mu);
+  const auto key = std::make_pair((int)dev.index(), C);
+  auto it = cache.find(key);
+  if (it != cache.end()) return it->second;
+  at::Tensor t = at::cat({at::zeros({1, C}, at::kFloat), at::ones({1, C}, at::kFloat)}).to(dev);
+  cache.emplace(key, t);
+  return t;
+}
+// the GEMM routes of conv2d_bn_act: one streaming pass over the GEMM's stored output
+inline at::Tensor affine_pass(const at::Tensor& c, const ConvAffine& af) {
+  const int64_t K = c.size(1);
+  const at::Tensor id = affine_identity_stats(c.device(), K);
+  auto y = at::empty_like(c);
+  check(dl_bn_apply(cbf(c), af.res, bf(y), af.scale, af.shift, f32(id), f32(id) + K, c.numel() / K, (int)K, 1,
+                    af.relu, cur_stream(c)),
+        "conv2d_bn_act (a GEMM-routed conv needs 64..2048 output channels, a power-of-two multiple of 8)");
+  return y;
+}
+
 at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t stride, int64_t pad, float* stats,
-                           int64_t groups, const c10::optional<at::Tensor>& cols) {
+                           int64_t groups, const c10::optional<at::Tensor>& cols, const ConvAffine* af) {
   expect_nhwc(x, "x");
   TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 4, "w must be a bf16 [Cout,Cin,R,S] GPU tensor");
   const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
@@ -1424,10 +1456,16 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
     const DlGemm g = gemm_desc(xr, false, wr, true, bf(y), K);  // y[M, K] = x[M, C] w[K, C]^T
     if (stats) gemm_store_stats(g, stats, stat_rows, xr, cur_stream(x));
     else gemm_store(g, xr, cur_stream(x));
-    return y;
+    return af ? affine_pass(y, *af) : y;
   }
   if (C % 64 == 0) {
     const DlConvGeom gm = geom(cbf(x), N, H, W, C, P, Q, stride, stride, R, S, -pad, 1, -pad, 1);
+    if (af) {
+      check(dl_conv_fwd_affine(gm, cbf(wk), R * S * C, (int)K, bf(y), (int)P, (int)Q, K, af->scale, af->shift, af->res,
+                               af->relu, cur_stream(x)),
+            "conv2d_bn_act");
+      return y;
+    }
     if (stats && dl_conv_fwd(gm, cbf(wk), R * S * C, (int)K, bf(y), (int)P, (int)Q, 1, 1, 0, 0, K, cur_stream(x),
                              stats, stat_rows) == 0)
       return y;
@@ -1449,6 +1487,12 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
     auto w2 = at::zeros({K, 256}, w.options());
     w2.index_copy_(1, stem_s2d_index(w.device()), wk.reshape({K, 147}));
     const DlConvGeom gs = geom(cbf(xs), N, H / 2, W / 2, 16, P, Q, 1, 1, 4, 4, -2, 1, -2, 1);
+    if (af) {
+      check(dl_conv_fwd_affine(gs, cbf(w2), 256, (int)K, bf(y), (int)P, (int)Q, K, af->scale, af->shift, af->res,
+                               af->relu, cur_stream(x)),
+            "conv2d_bn_act(stem)");
+      return y;
+    }
     if (stats && dl_conv_fwd(gs, cbf(w2), 256, (int)K, bf(y), (int)P, (int)Q, 1, 1, 0, 0, K, cur_stream(x), stats,
                              stat_rows) == 0)
       return y;
@@ -1469,6 +1513,9 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
   const int64_t Mc = col.size(0);
   if (sc.Kp % 64 == 0) {
     const DlConvGeom gc = geom(cbf(col), Mc, 1, 1, sc.Kp, 1, 1, 1, 1, 1, 1, 0, 1, 0, 1);
+    if (af && dl_conv_fwd_affine(gc, cbf(wp), sc.Kp, (int)K, bf(y), 1, 1, K, af->scale, af->shift, af->res, af->relu,
+                                 cur_stream(x)) == 0)
+      return y;
     if (stats && dl_conv_fwd(gc, cbf(wp), sc.Kp, (int)K, bf(y), 1, 1, 1, 1, 0, 0, K, cur_stream(x), stats,
                              stat_rows) == 0)
       return y;
@@ -1480,7 +1527,35 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
   const DlGemm g = gemm_desc(col, false, wp, true, bf(y), K);
   if (stats) gemm_store_stats(g, stats, stat_rows, col, cur_stream(x));
   else gemm_store(g, col, cur_stream(x));
-  return y;
+  return af ? affine_pass(y, *af) : y;
+}
+
+// Inference conv with a frozen BatchNorm folded into the epilogue:
+//   y = bf16(act(fmaf(float(bf16(conv(x, w))), scale[ch], shift[ch]) [+ res]))
+// i.e. conv2d_fwd followed by bn_apply(gamma = scale, beta = shift, mean = 0, rstd = 1), bit for bit.
+// Routed as conv2d_fwd: the conv.hip routes apply the expression in the kernel's epilogue, the
+// GEMM routes run the GEMM and one bn_apply pass.
+at::Tensor conv2d_bn_act(const at::Tensor& x, const at::Tensor& w, const at::Tensor& scale, const at::Tensor& shift,
+                         const c10::optional<at::Tensor>& res, bool relu, int64_t stride, int64_t pad) {
+  expect_nhwc(x, "x");
+  TORCH_CHECK(w.is_cuda() && w.scalar_type() == at::kBFloat16 && w.dim() == 4, "w must be a bf16 [Cout,Cin,R,S] GPU tensor");
+  expect(scale, at::kFloat, "scale");
+  expect(shift, at::kFloat, "shift");
+  const int64_t K = w.size(0);
+  TORCH_CHECK(scale.dim() == 1 && shift.dim() == 1 && scale.numel() == K && shift.numel() == K,
+              "conv2d_bn_act: scale / shift must be fp32 [Cout]");
+  TORCH_CHECK(K % 8 == 0, "conv2d_bn_act: Cout must be a multiple of 8");
+  TORCH_CHECK(stride >= 1 && pad >= 0, "conv2d_bn_act: stride / pad");
+  TORCH_CHECK(x.size(2) + 2 * pad >= w.size(2) && x.size(3) + 2 * pad >= w.size(3), "conv2d_bn_act: empty output");
+  if (res.has_value()) {
+    expect_nhwc(*res, "res");
+    const int64_t P = conv_out(x.size(2), w.size(2), stride, pad), Q = conv_out(x.size(3), w.size(3), stride, pad);
+    TORCH_CHECK(res->dim() == 4 && res->size(0) == x.size(0) && res->size(1) == K && res->size(2) == P &&
+                    res->size(3) == Q,
+                "conv2d_bn_act: res must have the output's shape");
+  }
+  const ConvAffine af{f32(scale), f32(shift), res.has_value() ? cbf(*res) : nullptr, relu};
+  return conv2d_fwd_impl(x, w, stride, pad, nullptr, 1, c10::nullopt, &af);
 }
 
 // Tap-transposed data-gradient weights of every parity class of a strided conv, in (a, b) order:
@@ -1772,6 +1847,7 @@ void conv2d_wgrad(const at::Tensor& dy_in, const at::Tensor& x, at::Tensor dw, i
 
 TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("conv2d_fwd", &conv2d_fwd);
+  m.impl("conv2d_bn_act", &conv2d_bn_act);
   m.impl("conv2d_fwd_stats", &conv2d_fwd_stats);
   m.impl("im2col_stem", &im2col_stem);
   m.impl("conv2d_dgrad_bn", &conv2d_dgrad_bn);

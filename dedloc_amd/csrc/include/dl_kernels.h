@@ -203,6 +203,11 @@ struct DlConvGeom {
 int dl_conv_fwd(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, int osh, int osw,
                 int oh0, int ow0, long ldo, hipStream_t st, float* stats = nullptr, long stat_rows = 0,
                 const DlBnBwdEpi* bn = nullptr);  // bn (needs stats): BN-backward preparation epilogue
+// dl_conv_fwd (dense output: stride-1 rows, row stride ldo) with a frozen BatchNorm in the epilogue:
+// out = bf16(act(fmaf(float(bf16(conv)), scale[ch], shift[ch]) [+ res])), scale / shift fp32 [N],
+// res (optional) in the output's layout, N a multiple of 8; no statistics
+int dl_conv_fwd_affine(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, long ldo,
+                       const float* scale, const float* shift, const bf16_t* res, int relu, hipStream_t st);
 // several independent forward jobs (same output tensor / channel count / epilogue, e.g. the parity
 // classes of a strided data gradient) in ONE launch; at most 4 jobs, all of one kernel variant
 // (-1 and nothing launched otherwise)

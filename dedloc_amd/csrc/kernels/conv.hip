@@ -26,6 +26,7 @@
 // operand roles so each lane owns 4 consecutive output channels of one pixel (8-byte NHWC stores).
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "dl_common.h"
 #include "dl_kernels.h"
@@ -165,12 +166,25 @@ __device__ __forceinline__ void st_kin_n(const StageN<U>& s, uint8_t* img) {
   }
 }
 
+// The inference epilogue's operands (AFF kernels).  They ride behind the FwdMulti block, so the
+// argument layout, and with it the code, of every other instantiation is what it was without them.
+struct FwdAffine : FwdMulti {
+  const float* scale;  // [N] fp32
+  const float* shift;  // [N] fp32
+  const bf16_t* res;   // optional residual, the output's layout (row stride ldo)
+  int relu;
+};
+
 // SUB: C < 64 (a divisor of 64, multiple of 8): a 64-deep k-step spans 64 / C taps, so each thread
 // decodes the tap of its own 8-channel chunk (the space-to-depth stem: C = 16, 4 x 4 taps)
 // MULTI: the launch holds several jobs (FwdMulti); otherwise a[0] only, with static argument
 // offsets (a run-time job index in every launch cost the forward 3-4%)
-template <int TM_, int TN_, bool SUB = false, bool MULTI = false>
-__global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(const FwdMulti P) {
+// AFF (non-MULTI): the inference epilogue of a frozen BatchNorm — the stored value is
+// bf16(act(fmaf(float(bf16(conv)), scale[ch], shift[ch]) [+ res])), bn_apply_kernel's expression on
+// the value the plain kernel stores; no statistics, no atomics
+template <int TM_, int TN_, bool SUB = false, bool MULTI = false, bool AFF = false>
+__global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(const std::conditional_t<AFF, FwdAffine, FwdMulti> P) {
+  static_assert(!(AFF && MULTI), "the inference epilogue is single-job");
   constexpr int WN = TN_ / 64, UA = TM_ / 32, UB = TN_ / 32;
   int job = 0, bid;
   if constexpr (MULTI) {
@@ -342,7 +356,7 @@ __global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(const FwdMulti P) {
     // bnbwd: this thread's 8 channels of the tile's statistics group (mean / rstd, and the ReLU
     // mask's scale / shift when it comes from the BN input X)
     float bmu[8], brs[8], bsc[8], bsh[8];
-    if (p.bnbwd) {
+    if (!AFF && p.bnbwd) {
       const int ch0 = min(n0 + (tid % CPR) * 8, p.N - 8);
       const long go = (long)(m0 / p.stat_rows) * p.N + ch0;
 #pragma unroll
@@ -352,6 +366,16 @@ __global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(const FwdMulti P) {
         bmu[e] = -mu * brs[e];  // xhat = x * rstd + bmu
         bsc[e] = p.bn.Y ? 0.f : p.bn.gamma[ch0 + e] * brs[e];
         bsh[e] = p.bn.Y ? 0.f : p.bn.beta[ch0 + e] - mu * bsc[e];
+      }
+    }
+    // AFF: this thread's 8 channels of scale / shift, once per tile
+    float asc[8], ash[8];
+    if constexpr (AFF) {
+      const int ch0 = min(n0 + (tid % CPR) * 8, p.N - 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        asc[e] = P.scale[ch0 + e];
+        ash[e] = P.shift[ch0 + e];
       }
     }
 #pragma unroll
@@ -364,7 +388,18 @@ __global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(const FwdMulti P) {
         const int i = fdiv(r, g.J, rJ), j = r - i * g.J;
         const long pix = (long)(n * p.OH + i * p.osh + p.oh0) * p.OW + j * p.osw + p.ow0;
         bf16_t* orow = p.out + pix * p.ldo;
-        if (p.bnbwd) {  // g = dY masked by the BN's ReLU; the BN backward's two sums
+        if constexpr (AFF) {
+          float f[8], rr[8];
+          unpack8_bf16(v, f);
+          if (P.res) load_bf16<8>(P.res + pix * p.ldo + ch, rr);  // uniform
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            float o = fmaf(f[e], asc[e], ash[e]);
+            if (P.res) o += rr[e];
+            f[e] = P.relu && o < 0.f ? 0.f : o;  // NaN passes, as bn_apply_kernel
+          }
+          *reinterpret_cast<uint4*>(orow + ch) = pack8_bf16(f);
+        } else if (p.bnbwd) {  // g = dY masked by the BN's ReLU; the BN backward's two sums
           float f[8], xv[8], yv[8];
           unpack8_bf16(v, f);
           load_bf16<8>(p.bn.X + pix * p.bn.ldx + ch, xv);
@@ -389,7 +424,7 @@ __global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(const FwdMulti P) {
         } else {
           *reinterpret_cast<uint4*>(orow + ch) = v;
         }
-        if (p.stats && !p.bnbwd) {
+        if (!AFF && p.stats && !p.bnbwd) {
           float f[8];
           unpack8_bf16(v, f);
 #pragma unroll
@@ -400,7 +435,7 @@ __global__ __launch_bounds__(NT, 2) void conv_fwd_kernel(const FwdMulti P) {
         }
       }
     }
-    if (p.stats) {
+    if (!AFF && p.stats) {
       // Atomics are issue-bound (one wave-instruction per ~50 ns per CU, MI355X_MICROARCH.md), so
       // the tile's 2 x TN_ statistics are folded before they leave: the lanes of a wave that share
       // a chunk (shuffles), then the 4 waves in the (drained) staging buffer, and one thread per
@@ -1022,6 +1057,57 @@ int dl_conv_fwd(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* o
                 int oh0, int ow0, long ldo, hipStream_t st, float* stats, long stat_rows, const DlBnBwdEpi* bn) {
   const DlConvFwdJob job{g, w, ldw, oh0, ow0, stat_rows};
   return dl_conv_fwd_multi(&job, 1, N, out, OH, OW, osh, osw, ldo, st, stats, bn);
+}
+
+// dl_conv_fwd with the inference epilogue (one job, no statistics): the same validation, variant
+// choice and grid as dl_conv_fwd_multi makes for that job, on the AFF instantiations
+int dl_conv_fwd_affine(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, long ldo,
+                       const float* scale, const float* shift, const bf16_t* res, int relu, hipStream_t st) {
+  if (N < 8 || N % 8 || ldo % 8 || !scale || !shift) return -1;
+  const bool sub = g.C < BK;
+  if ((sub ? (BK % g.C || g.C % 8) : g.C % BK) || ldw % 8 || g.I < 0 || g.J < 0) return -1;
+  if (sub && (g.TR * g.TS * g.C) % BK) return -1;
+  const long M = (long)g.Nimg * g.I * g.J;
+  if (M >= (1L << 24)) return -1;  // fdiv exactness bound (pixel decodes)
+  const long img_bytes = 2L * g.Nimg * g.H * g.W * g.C, w_bytes = 2L * N * ldw;
+  if (img_bytes >= (1L << 31) || w_bytes >= (1L << 31)) return -1;  // 32-bit buffer offsets
+  if (M == 0) return 0;
+  const bool narrow = N <= 64;
+  const int TMv = narrow ? 256 : BM, TNv = narrow ? 64 : BN;
+  const long tiles = ((M + TMv - 1) / TMv) * ((N + TNv - 1) / TNv);
+  if (tiles >= (1L << 31)) return -1;
+  static bool attr = false;
+  if (!attr) {
+    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN, false, false, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM + BN) * 128));
+    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<256, 64, false, false, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128));
+    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN, true, false, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM + BN) * 128));
+    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<256, 64, true, false, true>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128));
+    attr = true;
+  }
+  const int tpw = (int)std::max<long>(1, tiles / DL_CONV_FWD_WG);
+  FwdAffine P{};
+  P.a[0] = FwdArgs{g, w, ldw, N, out, OH, OW, 1, 1, 0, 0, ldo, g.Nimg * g.I * g.J, g.TR * g.TS * g.C,
+                   (unsigned)img_bytes, (unsigned)w_bytes, tpw, nullptr, 0, DlBnBwdEpi{}, 0};
+  P.n = 1;
+  P.wg_begin[1] = (int)((tiles + tpw - 1) / tpw);
+  P.scale = scale;
+  P.shift = shift;
+  P.res = res;
+  P.relu = relu;
+  const dim3 grid(P.wg_begin[1]);
+  const int lds = 2 * (TMv + TNv) * 128;
+  if (sub) {
+    if (narrow) conv_fwd_kernel<256, 64, true, false, true><<<grid, NT, lds, st>>>(P);
+    else conv_fwd_kernel<BM, BN, true, false, true><<<grid, NT, lds, st>>>(P);
+  } else {
+    if (narrow) conv_fwd_kernel<256, 64, false, false, true><<<grid, NT, lds, st>>>(P);
+    else conv_fwd_kernel<BM, BN, false, false, true><<<grid, NT, lds, st>>>(P);
+  }
+  return 0;
 }
 
 // Split count of dl_conv_wgrad: the (long) pixel reduction is split so that ~`target` workgroups

@@ -10,6 +10,8 @@ in ``torch.ops.dedloc.multicrop_ragged`` (csrc/kernels/augment.hip).  Decoding r
 
 ``ImageFolderEvalStream`` is the labelled, unshuffled view of the same directories for evaluation
 (``training/swav_eval.py``): every image once, under Resize + CenterCrop through the same sampler.
+``ImageFolderLabelledStream`` is the labelled, per-epoch reshuffled training view for the linear
+evaluation (``training/swav_linear.py``): RandomResizedCrop + flip, no colour or blur.
 
 Besides image files the dataset serves ``.npy`` files holding a uint8 [H, W, 3] array: a
 pre-decoded form that needs no PIL and no JPEG decode.
@@ -263,6 +265,55 @@ class ImageFolderEvalStream(_RaggedBatcher):
             data, meta, H, W = self._pack(imgs)
             params = aug.center_params(torch.arange(len(imgs)), H, W, self.size, self.resize)
             labels = self.labels[s:s + B]
+            if data.is_cuda:
+                params = params.pin_memory().to(data.device, non_blocking=True)
+                labels = labels.pin_memory().to(data.device, non_blocking=True)
+            x = torch.ops.dedloc.multicrop_ragged(data, meta, params, self.size, aug.rad, list(aug.mean), list(aug.std))
+            yield x, labels
+
+
+class ImageFolderLabelledStream(_RaggedBatcher):
+    """The labelled training view of an image directory for the linear evaluation
+    (``training/swav_linear.py``): the images ``indices`` (default: all) in a fresh fixed-seed
+    permutation per epoch, each under a fresh ``RandomResizedCrop(size)`` + ``RandomHorizontalFlip`` +
+    Normalize (``MultiCropAugment.crop_flip_params`` through the ragged GPU sampler).
+    ``epoch(e)`` yields ``(images [b, 3, size, size] bf16 channels-last, labels [b] int64)`` on the
+    device; the last batch of an epoch is short.  Epoch ``e``'s order and crops depend on ``seed``
+    and ``e`` only."""
+
+    def __init__(self, dataset: ImageFolderDataset, batch_size: int, device, indices=None, labels=None,
+                 size: int = 224, seed: int = 0, num_workers: int = 8, prefetch_batches: int = 2):
+        self.prefetch_batches = max(0, int(prefetch_batches))
+        super().__init__(device, dataset, num_workers, self.prefetch_batches)
+        self.batch_size, self.size, self.seed = int(batch_size), int(size), int(seed)
+        self.indices = list(range(len(dataset))) if indices is None else [int(i) for i in indices]
+        self.labels = dataset.labels[self.indices] if labels is None else labels
+        self.augment = MultiCropAugment()  # mean / std of the training pipeline
+
+    def __len__(self):
+        return len(self.indices)
+
+    def steps_per_epoch(self) -> int:
+        return -(-len(self.indices) // self.batch_size)
+
+    def epoch(self, e: int):
+        import dedloc_amd.ops  # noqa: F401  (registers dedloc::multicrop_ragged)
+
+        B, aug = self.batch_size, self.augment
+        gen = torch.Generator().manual_seed(self.seed + 7919 * int(e))
+        order = torch.randperm(len(self.indices), generator=gen).tolist()
+        starts = list(range(0, len(order), B))
+        pending: deque = deque()
+        nxt = 0
+        for s in starts:
+            while nxt < len(starts) and len(pending) < self.prefetch_batches + 1:
+                chunk = order[starts[nxt]:starts[nxt] + B]
+                pending.append([self._pool.submit(self.dataset.load, self.indices[k]) for k in chunk])
+                nxt += 1
+            imgs = [f.result() for f in pending.popleft()]
+            data, meta, H, W = self._pack(imgs)
+            params = aug.crop_flip_params(torch.arange(len(imgs)), H, W, gen)
+            labels = self.labels[order[s:s + B]]
             if data.is_cuda:
                 params = params.pin_memory().to(data.device, non_blocking=True)
                 labels = labels.pin_memory().to(data.device, non_blocking=True)

@@ -176,14 +176,12 @@ class MultiCropAugment:
         t = torch.stack([bright, contrast, sat, apply, grey], 1)
         return flip, torch.cat([t, M.reshape(nb, 9), sigma.view(-1, 1)], 1)
 
-    def sample_params_ragged(self, src: torch.Tensor, H: torch.Tensor, W: torch.Tensor, scale,
-                             gen: torch.Generator) -> torch.Tensor:
-        """Host-side draws for one crop resolution over images of different sizes ([nb] rows ``src``
-        of the batch's image table, their heights ``H`` and widths ``W``): [nb, 20] fp32 table for
-        ``dedloc::multicrop_ragged`` (columns 0-4: row, box left, top, width (negative: mirrored),
-        height, in pixels).  The box is torchvision's ``RandomResizedCrop.get_params``, vectorised:
-        ten attempts, the first that fits wins, else the centred box with its ratio clamped."""
-        nb = src.shape[0]
+    @staticmethod
+    def _rrc_box(H: torch.Tensor, W: torch.Tensor, scale, gen: torch.Generator):
+        """torchvision's ``RandomResizedCrop.get_params`` (ratio 3/4..4/3), vectorised over images of
+        heights ``H`` and widths ``W``: ten attempts, the first that fits wins, else the centred box
+        with its ratio clamped.  Returns float64 (left, top, width, height) in pixels."""
+        nb = H.shape[0]
         Hd, Wd = H.double(), W.double()
         tries = 10
         area = torch.empty(nb, tries, dtype=torch.float64).uniform_(scale[0], scale[1], generator=gen) * (Hd * Wd)[:, None]
@@ -202,8 +200,32 @@ class MultiCropAugment:
         w, h = torch.where(fits, w, fw), torch.where(fits, h, fh)
         i = torch.where(fits, torch.floor(ui * (Hd - h + 1)).clamp(max=Hd - h), torch.floor((Hd - h) / 2))
         j = torch.where(fits, torch.floor(uj * (Wd - w + 1)).clamp(max=Wd - w), torch.floor((Wd - w) / 2))
-        flip, tail = self._draw_flip_color_blur(nb, gen)
+        return j, i, w, h
+
+    def sample_params_ragged(self, src: torch.Tensor, H: torch.Tensor, W: torch.Tensor, scale,
+                             gen: torch.Generator) -> torch.Tensor:
+        """Host-side draws for one crop resolution over images of different sizes ([nb] rows ``src``
+        of the batch's image table, their heights ``H`` and widths ``W``): [nb, 20] fp32 table for
+        ``dedloc::multicrop_ragged`` (columns 0-4: row, box left, top, width (negative: mirrored),
+        height, in pixels).  The box is ``_rrc_box``."""
+        j, i, w, h = self._rrc_box(H, W, scale, gen)
+        flip, tail = self._draw_flip_color_blur(src.shape[0], gen)
         return torch.cat([torch.stack([src.double(), j, i, w * flip, h], 1), tail], 1).float()
+
+    @classmethod
+    def crop_flip_params(cls, src: torch.Tensor, H: torch.Tensor, W: torch.Tensor, gen: torch.Generator,
+                         scale=(0.08, 1.0), flip_p: float = 0.5) -> torch.Tensor:
+        """The linear-evaluation train transform ``RandomResizedCrop(scale, ratio 3/4..4/3)`` +
+        ``RandomHorizontalFlip(flip_p)`` as a [nb, 20] table for ``dedloc::multicrop_ragged``: the
+        box of ``_rrc_box``, the mirror in the width's sign, and the colour and blur columns at
+        identity as in ``center_params``."""
+        j, i, w, h = cls._rrc_box(H, W, scale, gen)
+        flip = torch.where(torch.rand(src.shape[0], dtype=torch.float64, generator=gen) < flip_p, -1.0, 1.0).double()
+        p = torch.zeros(src.shape[0], 20, dtype=torch.float64)
+        p[:, 0], p[:, 1], p[:, 2], p[:, 3], p[:, 4] = src.double(), j, i, w * flip, h
+        p[:, 5:8] = 1.0
+        p[:, 10], p[:, 14], p[:, 18] = 1.0, 1.0, 1.0
+        return p.float()
 
     @staticmethod
     def center_params(src: torch.Tensor, H: torch.Tensor, W: torch.Tensor, size: int, resize: int) -> torch.Tensor:

@@ -388,7 +388,8 @@ class BNAct(nn.BatchNorm2d):
 
 def _bn_eval(m, x, res, relu: bool):
     """Inference BatchNorm with the running statistics: y = x * scale + shift (+ res) (ReLU), as one
-    broadcast expression in the input's layout (not on the training path)."""
+    broadcast expression in the input's layout (not on the training path; ``FrozenTrunk`` is the
+    inference path on the kernels, with this scale / shift in the conv's epilogue)."""
     scale = m.weight.float() * torch.rsqrt(m.running_var.float() + m.eps)
     shift = m.bias.float() - m.running_mean.float() * scale
     shp = (1, -1) + (1,) * (x.dim() - 2)
@@ -650,6 +651,66 @@ class ResNet50Trunk(nn.Module):
         for stage in (self.layer1, self.layer2, self.layer3):
             x = _SegmentReplay.apply(x, stage) if replay and x.requires_grad else stage(x)
         return global_avgpool(self.layer4(x))
+
+
+class FrozenTrunk:
+    """Inference snapshot of a ``ResNet50Trunk``: ``[N, 3, H, W]`` bf16 channels-last images ->
+    ``[N, 2048]`` bf16 pooled features, one ``conv2d_bn_act`` per conv (the BatchNorm's running
+    statistics folded to a per-channel scale / shift in the conv's epilogue; bn3's residual add and
+    ReLU in conv3's call, the downsample branch without ReLU), the two pool operators around them.
+
+    It is a SNAPSHOT taken at construction under ``no_grad``: its own bf16 copy of every conv weight
+    and ``scale = weight * rsqrt(running_var + eps)``, ``shift = bias - running_mean * scale`` in fp32
+    per BatchNorm.  It keeps no reference to the model, never touches it (parameters, running
+    statistics, counters, training flag) and does not follow a later optimizer step: build a new one
+    per evaluation.  It creates no autograd nodes, gradient links, pass workspaces or side streams.
+
+    ``fused``: the conv classes (``CLASSES``) whose convs run as one ``conv2d_bn_act``; the others run
+    the two-kernel form ``bn_apply(conv2d_fwd(x, w), ...)``, which computes the same bits (a
+    measurement switch, and the fallback for a class where the fused epilogue does not win).  Inside
+    ``conv2d_bn_act`` the stride-1 1x1 convs that take the GEMM route are two kernels either way.
+    """
+
+    CLASSES = ("stem", "3x3", "1x1", "strided1x1")
+
+    def __init__(self, trunk: "ResNet50Trunk", fused=True):
+        self.fused = frozenset(self.CLASSES if fused is True else (() if not fused else fused))
+        if not self.fused <= set(self.CLASSES):
+            raise ValueError(f"fused: conv classes out of {self.CLASSES}, got {sorted(self.fused)}")
+        with torch.no_grad():
+            self.stem = self._snap(trunk.conv1, trunk.bn1)
+            self.blocks = []
+            for stage in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
+                for b in stage:
+                    down = None if b.downsample is None else self._snap(b.downsample[0], b.downsample[1])
+                    self.blocks.append((self._snap(b.conv1, b.bn1), self._snap(b.conv2, b.bn2),
+                                        self._snap(b.conv3, b.bn3), down))
+
+    @staticmethod
+    def _snap(conv, bn):
+        w = conv.weight.detach().to(torch.bfloat16, copy=True).contiguous(memory_format=torch.channels_last)
+        scale = bn.weight.detach().float() * torch.rsqrt(bn.running_var.float() + bn.eps)
+        shift = bn.bias.detach().float() - bn.running_mean.float() * scale
+        k, s = conv.kernel_size[0], conv.stride[0]
+        cls = "stem" if conv.in_channels % 64 else "3x3" if k == 3 else "1x1" if s == 1 else "strided1x1"
+        return (w, scale.contiguous(), shift.contiguous(), s, conv.padding[0], bool(bn.relu), cls,
+                torch.zeros_like(scale), torch.ones_like(scale))
+
+    def _conv(self, x, c, res=None):
+        w, scale, shift, stride, pad, relu, cls, zeros, ones = c
+        if cls in self.fused:
+            return torch.ops.dedloc.conv2d_bn_act(x, w, scale, shift, res, relu, stride, pad)
+        y = torch.ops.dedloc.conv2d_fwd(x, w, stride, pad)
+        return torch.ops.dedloc.bn_apply(y, res, scale, shift, zeros, ones, relu, 1)
+
+    @torch.no_grad()
+    def __call__(self, x: torch.Tensor) -> torch.Tensor:
+        x = _require_nhwc_bf16(x, "FrozenTrunk input")
+        x = torch.ops.dedloc.maxpool_fwd(self._conv(x, self.stem))[0]
+        for c1, c2, c3, down in self.blocks:
+            idt = x if down is None else self._conv(x, down)
+            x = self._conv(self._conv(self._conv(x, c1), c2), c3, idt)
+        return torch.ops.dedloc.avgpool_fwd(x)
 
 
 class _HeadLinearFn(torch.autograd.Function):
@@ -1006,6 +1067,12 @@ class SwAVModel(nn.Module):
             self.set_bn_stat_groups(1)
             f = self.trunk(x)
             return f if feature == "trunk" else self.heads[0].projection_head(f)
+
+    def frozen_trunk(self, fused=True) -> FrozenTrunk:
+        """An inference snapshot of the trunk as it is now (``FrozenTrunk``): BatchNorm folded into
+        the convs' epilogues, nothing of the model touched or referenced.  Rebuild it after the model
+        has changed (per evaluation)."""
+        return FrozenTrunk(self.trunk, fused)
 
     def _forward(self, crops):
         groups, i = [], 0

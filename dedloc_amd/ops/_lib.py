@@ -94,6 +94,8 @@ _SCHEMAS = [
     "conv2d_fwd(Tensor x, Tensor w, int stride, int pad, Tensor? cols=None) -> Tensor",
     "conv2d_fwd_stats(Tensor x, Tensor w, int stride, int pad, Tensor(a!) sums, int groups, Tensor? cols=None) "
     "-> Tensor",
+    "conv2d_bn_act(Tensor x, Tensor w, Tensor scale, Tensor shift, Tensor? res, bool relu, int stride, int pad) "
+    "-> Tensor",
     "im2col_stem(Tensor x, int R, int S, int stride, int pad) -> Tensor",
     "conv2d_dgrad(Tensor dy, Tensor w, int stride, int pad, int H, int W, Tensor? residual=None, "
     "Tensor[]? wds=None) -> Tensor",
@@ -927,6 +929,16 @@ def _conv2d_fwd_stats_cpu(x, w, stride, pad, sums, groups, cols=None):
     yg = y.float().reshape(groups, -1, *y.shape[1:])
     sums.view(groups, 2, -1).add_(torch.stack([yg.sum(dim=(1, 3, 4)), (yg * yg).sum(dim=(1, 3, 4))], 1))
     return y
+
+
+@_impl("conv2d_bn_act")
+def _conv2d_bn_act_cpu(x, w, scale, shift, res, relu, stride, pad):
+    # inference conv + frozen BatchNorm: the composition of the two CPU ops above, bitwise
+    assert scale.dtype == torch.float32 and shift.dtype == torch.float32, "scale / shift must be fp32"
+    assert scale.shape == (w.shape[0],) and shift.shape == (w.shape[0],), "scale / shift must be [Cout]"
+    c = _conv2d_fwd_cpu(x, w, stride, pad)
+    assert res is None or res.shape == c.shape, "res must have the output's shape"
+    return _bn_apply_cpu(c, res, scale, shift, torch.zeros_like(scale), torch.ones_like(scale), relu, 1)
 
 
 @_impl("conv2d_dgrad")

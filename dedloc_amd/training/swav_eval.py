@@ -21,20 +21,29 @@ from .. import ops
 QUERY_CHUNK = 4096  # query rows per knn_classify call (bounds the kernel's candidate-list scratch)
 
 
-def extract_features(model, stream, feature: str = "trunk") -> Tuple[torch.Tensor, torch.Tensor]:
+def extract_features(model, stream, feature: str = "trunk", frozen: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """Every image of ``stream`` (an iterable of ``(images, labels)`` batches) through ``model`` in
     eval mode: L2-normalised bf16 features [n, D] (``trunk``: D = 2048, ``head``: D = 128) and their
-    labels [n] int64, on the device.  The model's training flag is restored on the way out."""
+    labels [n] int64, on the device.  The model's training flag is restored on the way out.
+
+    ``frozen``: the trunk runs as ``model.frozen_trunk()`` (a snapshot taken here, BatchNorm folded
+    into the convs' epilogues); the head's projection, where asked for, runs on its output as above."""
     if feature not in ("trunk", "head"):
         raise ValueError(f"feature must be 'trunk' or 'head', got {feature!r}")
     was_training = model.training
     feats, labels = [], []
     try:
         model.eval()
+        trunk = model.frozen_trunk() if frozen else None
         with torch.no_grad():
             for x, y in stream:
                 with torch.autocast(device_type=x.device.type, dtype=torch.bfloat16, enabled=x.is_cuda):
-                    f = model.features(x, feature)
+                    if trunk is None:
+                        f = model.features(x, feature)
+                    else:
+                        f = trunk(x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last))
+                        if feature == "head":
+                            f = model.heads[0].projection_head(f)
                 f, _ = torch.ops.dedloc.l2norm_fwd(f.to(torch.bfloat16).contiguous(), 1e-12)
                 feats.append(f)
                 labels.append(y)
@@ -46,12 +55,13 @@ def extract_features(model, stream, feature: str = "trunk") -> Tuple[torch.Tenso
 
 
 def knn_evaluate(model, bank_stream, query_stream, k: int = 200, sigma: float = 0.1, feature: str = "trunk",
-                 num_classes: int | None = None) -> Dict[str, float]:
+                 num_classes: int | None = None, frozen: bool = False) -> Dict[str, float]:
     """Weighted kNN accuracy of the query set against the bank.  ``num_classes`` defaults to the
     bank stream's dataset's class count.  ``knn_samples`` counts the queries that carry a class
-    label; a query whose class got no vote from its neighbours is a miss."""
-    bank, bank_labels = extract_features(model, bank_stream, feature)
-    query, targets = extract_features(model, query_stream, feature)
+    label; a query whose class got no vote from its neighbours is a miss.  ``frozen``: see
+    ``extract_features``."""
+    bank, bank_labels = extract_features(model, bank_stream, feature, frozen)
+    query, targets = extract_features(model, query_stream, feature, frozen)
     if num_classes is None:
         num_classes = len(bank_stream.dataset.classes)
     k = max(1, min(int(k), bank.shape[0]))
@@ -116,7 +126,8 @@ def build_knn_sets(cfg) -> dict:
             "size": int(nn_cfg.get("CENTER_CROP", 224)), "resize": int(nn_cfg.get("RESIZE", 256)),
             "batch_size": int(test.get("BATCHSIZE_PER_REPLICA", 64)),
             "num_workers": int(train.get("NUM_DATALOADER_WORKERS", 8)), "k": int(nn_cfg.get("TOPK", 200)),
-            "sigma": float(nn_cfg.get("SIGMA", 0.1)), "feature": str(nn_cfg.get("FEATURE", "trunk"))}
+            "sigma": float(nn_cfg.get("SIGMA", 0.1)), "feature": str(nn_cfg.get("FEATURE", "trunk")),
+            "frozen": bool(nn_cfg.get("FROZEN_TRUNK", False))}
 
 
 def knn_evaluate_sets(model, sets: dict, device) -> Dict[str, float]:
@@ -129,7 +140,8 @@ def knn_evaluate_sets(model, sets: dict, device) -> Dict[str, float]:
     query = ImageFolderEvalStream(sets["query"], sets["batch_size"], device, indices=sets["query_indices"], **kw)
     query.labels = sets["query_labels"][sets["query_indices"]]
     try:
-        return knn_evaluate(model, bank, query, k=sets["k"], sigma=sets["sigma"], feature=sets["feature"])
+        return knn_evaluate(model, bank, query, k=sets["k"], sigma=sets["sigma"], feature=sets["feature"],
+                            frozen=sets.get("frozen", False))
     finally:
         bank.close()
         query.close()
