@@ -161,6 +161,96 @@ __device__ __forceinline__ void stage_pre(const bf16_t* const (&base)[2], long k
   for (int j = 0; j < 2; ++j) dma16(base[j] + koff, slot + (j * 8 + w) * 1024);
 }
 
+// ---- K loop without address arithmetic (KLOOP2) ------------------------------------------------
+// LDS slot map: the two halves and both buffer parities of an operand lie inside one 64 KiB region,
+//   A region at 0, B region at 64 KiB;  half h, parity p at h * 32 KiB + p * 16 KiB,
+// so that every fragment read is `loop-invariant VGPR + immediate` (the ds immediate reaches 65535)
+// with the parity a compile-time constant of a K-tile body instantiated for both:
+//   A0p0 A0p1 A1p0 A1p1 | B0p0 B0p1 B1p0 B1p1      (16 KiB each; 128 KiB as before)
+// Restaging, restated for this map: the eight images are the earlier map's eight under other
+// addresses, one per (operand half, parity), none shared.  K-tile t (parity P) reads A0/B0 in phase
+// 0, B1 in phase 1, A1 in phase 2 (B0 stays in registers for phase 3) and issues the DMAs into
+// A1/P^1 (phase 0), B0/P^1 (1), A0/P (2), B1/P (3).  The images of parity P^1 were last read by
+// K-tile t-1 (A1 in its phase 2, B0 in its phase 0): two phases or more before their restaging.
+// A0/P is restaged in phase 2, two phases after its read in phase 0; B1/P in phase 3, two phases
+// after its read in phase 1.  So every image is still restaged no sooner than two phases after its
+// last read, which covers the group that runs one barrier behind.  The swizzles inside an image
+// are unchanged and every image starts at a multiple of 16 KiB, so the bank pattern of every read
+// and DMA write is the one simulated for the earlier map.  The epilogue's per-wave 16 KiB staging
+// regions (smem + w * 16 KiB) do not move.
+constexpr uint32_t REGION_B = 4 * HALF;
+__host__ __device__ constexpr uint32_t himm(int half, int par) { return half * 2 * HALF + par * HALF; }
+
+// global_load_lds with a scalar 64-bit base and a 32-bit unsigned per-lane byte offset
+__device__ __forceinline__ void dma16s(const bf16_t* sbase, uint32_t voff, uint32_t lds_dst) {
+  const uint32_t m0 = __builtin_amdgcn_readfirstlane(lds_dst);
+  asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(m0), "v"(voff), "s"(sbase) : "memory", "m0");
+}
+
+// Per-lane byte offset of both LDS-DMA pieces of a half-tile from the tile's first element (row r0
+// at the K-tile's first k): src_base's row / chunk / column part, computed once.  The K advance is
+// on the scalar base.  dl_gemm8 bounds ld so that 255 rows (K-inner) / 63 k-rows (K-outer) fit 32 bits.
+template <bool KO, bool ISB>
+__device__ __forceinline__ void src_off(long ld, int r0, int rows_valid, int half, int w, int lane,
+                                        uint32_t (&off)[2]) {
+  const uint32_t pitch = (uint32_t)ld * 2;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int region = j * 8 + w;
+    if constexpr (!KO) {
+      const int lrow = region * 8 + (lane >> 3);
+      const int c = (lane & 7) ^ kin_swz(lrow);
+      const int grow = min(r0 + half_to_tile<ISB>(lrow, half), rows_valid - 1);  // M tail: clamp
+      off[j] = (uint32_t)(grow - r0) * pitch + c * 16;
+    } else {
+      const int k = region * 4 + (lane >> 4);
+      const int c = (lane & 15) ^ kout_swz(k);
+      off[j] = (uint32_t)k * pitch + colperm<ISB>(half_to_tile<ISB>(c * 8, half)) * 2;
+    }
+  }
+}
+
+// Loop-invariant per-lane LDS addresses of an operand's fragments (NF fragments of 16 rows from r0;
+// `base` = the operand region's LDS address).  What cannot go into the read's immediate gets a
+// register:  K-inner, the k-step (it enters the chunk XOR; 16 more rows are +2048 B with the same
+// swizzle): 2 registers;  K-outer, the fragment (its column chunk enters the XOR) and the lo / hi
+// k-rows (kr, kr + 4: a lane-dependent swizzle difference): 2 NF registers, the k-step being
+// +32 k-rows = +8192 B with the same swizzle.
+template <bool KO, int NF>
+__device__ __forceinline__ void frag_addr(uint32_t base, int r0, int lane, uint32_t (&reg)[KO ? 2 * NF : 2]) {
+  if constexpr (!KO) {
+    const int row = r0 + (lane & 15);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks) reg[ks] = base + row * 128 + (((4 * ks + (lane >> 4)) ^ kin_swz(row)) << 4);
+  } else {
+    const int g = lane >> 4, i = lane & 15;
+    const int kr = 8 * g + (i >> 2);
+#pragma unroll
+    for (int f = 0; f < NF; ++f) {
+      const int col = r0 + 16 * f + 4 * (i & 3);
+      reg[2 * f] = base + kr * 256 + (((col >> 3) ^ kout_swz(kr)) << 4) + ((col & 7) << 1);
+      reg[2 * f + 1] = base + (kr + 4) * 256 + (((col >> 3) ^ kout_swz(kr + 4)) << 4) + ((col & 7) << 1);
+    }
+  }
+  // opaque from here on: the K loop adds compile-time constants only, which fold into the immediates
+#pragma unroll
+  for (int i = 0; i < (KO ? 2 * NF : 2); ++i) asm volatile("" : "+v"(reg[i]));
+}
+
+typedef __attribute__((address_space(3))) bf16x8 lds_bf16x8;
+
+// Fragment f, k-step ks of the half-tile image at `imm` (himm) inside the operand's region
+template <bool KO, int NF>
+__device__ __forceinline__ bf16x8 frag_at(const uint32_t (&reg)[KO ? 2 * NF : 2], int f, int ks, uint32_t imm) {
+  if constexpr (!KO) {
+    return *(const lds_bf16x8*)(reg[ks] + f * 2048 + imm);
+  } else {
+    const s4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(reg[2 * f] + ks * 8192 + imm));
+    const s4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s4*)(reg[2 * f + 1] + ks * 8192 + imm));
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7));
+  }
+}
+
 // MFMA operand fragment: 16 rows (r0..) x 32 k (k-step ks) of a half-tile image; lane l holds
 // (row r0 + (l & 15), k = 32 ks + 8 (l >> 4) + j), j = 0..7.
 template <bool KO>
@@ -239,8 +329,13 @@ __device__ __forceinline__ void tile_of(int bid, int tiles_m, int tiles_n, int G
 // The B0 fragments read in phase 0 stay in registers for phase 3 (16 more VGPRs) instead of being
 // read again — 24 instead of 28 KiB of LDS reads per wave and K-tile, and phase 3 issues no LDS
 // reads at all.
-// PRESRC: DMA source addresses from per-lane bases computed once (src_base / stage_pre)
-template <bool AKO, bool BKO, int EPI, bool PRESRC>
+// KLOOP2: the K loop without address arithmetic (slot map, dma16s, src_off, frag_addr above): a
+// two-K-tile body with compile-time buffer parity, every LDS read `invariant VGPR + immediate`,
+// every DMA `scalar base + per-lane offset`, the K advance one 64-bit scalar add per operand and
+// K-tile.  Same MFMA order, phases, barriers, stagger, counted waits and prefetch distance as the
+// earlier loop, which the two forms launch8 names still run:
+// PRESRC (earlier loop only): DMA source addresses from per-lane bases computed once (src_base / stage_pre)
+template <bool AKO, bool BKO, int EPI, bool PRESRC, bool KLOOP2>
 __global__ __launch_bounds__(NT, 2) void gemm8_kernel(Args p) {
   // EPI_BNBWD: + [4][256] fp32 BatchNorm coefficients of the tile's columns (read per pass from LDS
   // instead of holding 32 registers, which pay for reading the BN input one pass ahead)
@@ -273,6 +368,109 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(Args p) {
 #pragma unroll
         for (int d = 0; d < 2; ++d) acc[a][b][c][d] = floatx4{0.f, 0.f, 0.f, 0.f};
 
+  if constexpr (KLOOP2) {
+  // DMA sources: a scalar base per operand (tile origin at the K-tile being staged) plus per-lane
+  // offsets computed once; LDS destinations: this wave's 1 KiB pieces of a slot
+  uint32_t oA0[2], oA1[2], oB0[2], oB1[2];
+  src_off<AKO, false>(p.lda, m0, p.M, 0, w, lane, oA0);
+  src_off<AKO, false>(p.lda, m0, p.M, 1, w, lane, oA1);
+  src_off<BKO, true>(p.ldb, n0, p.N, 0, w, lane, oB0);
+  src_off<BKO, true>(p.ldb, n0, p.N, 1, w, lane, oB1);
+  const bf16_t* sA = AKO ? p.A + (long)kbase * p.lda + m0 : p.A + (long)m0 * p.lda + kbase;
+  const bf16_t* sB = BKO ? p.B + (long)kbase * p.ldb + n0 : p.B + (long)n0 * p.ldb + kbase;
+  const long stepA = AKO ? BK * p.lda : (long)BK, stepB = BKO ? BK * p.ldb : (long)BK;
+  const uint32_t wdst = lds0 + w * 1024;
+  auto stage = [&](const bf16_t* sbase, const uint32_t (&off)[2], uint32_t slot) {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) dma16s(sbase, off[j], wdst + slot + j * 8192);
+  };
+  // K-tile t lives in buffer parity (t + nk) & 1, so the last two K-tiles (the peeled tails) always
+  // have parities 0 and 1 and an odd nk peels one leading K-tile instead of doubling the tails
+  const uint32_t par0 = (nk & 1) * HALF;
+  // prologue: tile 0 and the first two half-tiles (A0, B1) of tile 1, in stream order A0 B1 A1 B0
+  stage(sA, oA0, par0 + himm(0, 0));
+  stage(sB, oB1, par0 + REGION_B + himm(1, 0));
+  stage(sA, oA1, par0 + himm(1, 0));
+  stage(sB, oB0, par0 + REGION_B + himm(0, 0));
+  sA += stepA;
+  sB += stepB;  // from here on: the origin of the tile after the one being computed
+  if (nk > 1) {
+    stage(sA, oA0, (HALF - par0) + himm(0, 0));
+    stage(sB, oB1, (HALF - par0) + REGION_B + himm(1, 0));
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+  } else {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  }
+  __builtin_amdgcn_s_barrier();
+  if (wm == 1) __builtin_amdgcn_s_barrier();  // stagger, as below
+  uint32_t fa[AKO ? 8 : 2], fb[BKO ? 4 : 2];
+  frag_addr<AKO, 4>(lds0, wm * 64, lane, fa);
+  frag_addr<BKO, 2>(lds0 + REGION_B, wn * 32, lane, fb);
+  bf16x8 af[4][2], bfr[2][2], bf0[2][2];
+  // One K-tile in buffer parity P; M1 / M2: K-tiles t+1 / t+2 exist (prefetch them into P^1 / P)
+  auto ktile = [&](auto par, auto m1, auto m2) {
+    constexpr int P = decltype(par)::value;
+    constexpr bool M1 = decltype(m1)::value, M2 = decltype(m2)::value;
+    // ---- phase 0: quadrant (0,0); prefetch A1 of tile t+1
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) bf0[ni][ks] = frag_at<BKO, 2>(fb, ni, ks, himm(0, P));
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) af[mi][ks] = frag_at<AKO, 4>(fa, mi, ks, himm(0, P));
+    if constexpr (M1) stage(sA, oA1, himm(1, P ^ 1));
+    __builtin_amdgcn_s_barrier();
+    DL_MFMA_QUAD_B(0, 0, bf0);
+    __builtin_amdgcn_s_barrier();
+
+    // ---- phase 1: quadrant (0,1); prefetch B0 of tile t+1
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni) bfr[ni][ks] = frag_at<BKO, 2>(fb, ni, ks, himm(1, P));
+    if constexpr (M1) stage(sB, oB0, REGION_B + himm(0, P ^ 1));
+    __builtin_amdgcn_s_barrier();
+    DL_MFMA_QUAD(0, 1);
+    __builtin_amdgcn_s_barrier();
+
+    // ---- phase 2: quadrant (1,1); prefetch A0 of tile t+2
+#pragma unroll
+    for (int ks = 0; ks < 2; ++ks)
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) af[mi][ks] = frag_at<AKO, 4>(fa, mi, ks, himm(1, P));
+    if constexpr (M2) {
+      sA += stepA;
+      stage(sA, oA0, himm(0, P));
+    }
+    __builtin_amdgcn_s_barrier();
+    DL_MFMA_QUAD(1, 1);
+    __builtin_amdgcn_s_barrier();
+
+    // ---- phase 3: quadrant (1,0); prefetch B1 of tile t+2; retire tile t+1
+    if constexpr (M2) {
+      sB += stepB;
+      stage(sB, oB1, REGION_B + himm(1, P));
+      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    } else {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    __builtin_amdgcn_s_barrier();
+    DL_MFMA_QUAD_B(1, 0, bf0);
+    __builtin_amdgcn_s_barrier();
+  };
+  using P0 = std::integral_constant<int, 0>;
+  using P1 = std::integral_constant<int, 1>;
+  if (nk >= 3 && (nk & 1)) ktile(P1{}, std::true_type{}, std::true_type{});
+  for (int i = (nk - 2) >> 1; i > 0; --i) {
+    ktile(P0{}, std::true_type{}, std::true_type{});
+    ktile(P1{}, std::true_type{}, std::true_type{});
+  }
+  if (nk >= 2) ktile(P0{}, std::true_type{}, std::false_type{});
+  ktile(P1{}, std::false_type{}, std::false_type{});
+  } else {
   const bf16_t* bA0[2];
   const bf16_t* bA1[2];
   const bf16_t* bB0[2];
@@ -440,6 +638,7 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(Args p) {
       }
   }
 #undef DL_STAGE
+  }
   if (wm == 0) __builtin_amdgcn_s_barrier();  // balance the stagger: every wave passes the same barriers
   float* const bnt = reinterpret_cast<float*>(smem + SMEM);  // EPI_BNBWD: [brs | bxh | bsc | bsh][256]
   if constexpr (EPI == EPI_BNBWD) {
@@ -722,16 +921,33 @@ __global__ __launch_bounds__(NT, 2) void gemm8_kernel(Args p) {
 // a second persistent form that deferred no store but ran the operand prefetch on across the tile
 // seam (grid = CU count, the next tile's first K-tile retired by the last K-tile's counted wait):
 // bit-identical, no scratch, +0.06% on the micro-step (profiles/README.md, "gemm8 tile boundary").
+//
+// KLOOP2, the K loop without address arithmetic (invariant fragment addresses, scalar K advance of
+// the DMA sources), won its same-box A/B in every round for every form timed (weight gradients
+// -12..-13%, forward / data gradients -3..-10%, bias+GELU forms -6%, the SwAV statistics / BN-backward
+// forms -2..-4%; micro-step -5.2%: profiles/gemm8_kloop_addr_ab.jsonl) but two, which keep the loop
+// they had: GELU' with a K-inner weight (+1.3%: PRESRC loop) and GELU-with-derivative with a K-outer
+// weight (faster in each round's pair, but not every round against every round: per-K-tile loop).
+// Neither is on ALBERT's path (gemm_dmul and the K-inner gemm_gelu_d are).
 template <bool AKO, bool BKO, int EPI>
 int launch8(const Args& a, int splits, hipStream_t st) {
   const int tiles = ((a.M + BM - 1) / BM) * (a.N / BN);
   const dim3 grid(tiles * splits);
-  if constexpr (EPI == EPI_GELU || EPI == EPI_GELUD) gemm8_kernel<AKO, BKO, EPI, false><<<grid, NT, 0, st>>>(a);
-  else gemm8_kernel<AKO, BKO, EPI, true><<<grid, NT, 0, st>>>(a);
+  constexpr bool KLOOP2 = !(EPI == EPI_DGELU && !BKO) && !(EPI == EPI_GELUD && BKO);
+  constexpr bool PRESRC = EPI != EPI_GELU && EPI != EPI_GELUD;  // read by the earlier loop only
+  gemm8_kernel<AKO, BKO, EPI, PRESRC, KLOOP2><<<grid, NT, 0, st>>>(a);
   return 0;
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+// Largest leading dimension (elements) whose per-lane LDS-DMA byte offsets (src_off) fit 32 bits
+// unsigned: the last 16-byte chunk of tile row 255 (K-inner: 255 ld + 56 elements), or of k-row 63
+// at tile column 248 (K-outer: 63 ld + 248 elements), ends below 2^32.
+inline long ld_reach(bool kouter) {
+  const long last = (1L << 32) - 16;  // the highest byte offset a chunk may start at
+  return kouter ? (last / 2 - 248) / 63 : (last / 2 - 56) / 255;
+}
 
 }  // namespace
 
@@ -744,6 +960,7 @@ int dl_gemm8(const DlGemm& g, hipStream_t st) {
   if (N % BN || K % (BK * splits)) return -1;
   if (g.a_kouter && M % BM) return -1;
   if (g.lda % 8 || g.ldb % 8 || !aligned16(g.A) || !aligned16(g.B)) return -1;
+  if (g.lda > ld_reach(g.a_kouter) || g.ldb > ld_reach(g.b_kouter)) return -1;
   if (epi == EPI_F32) {
     if (!g.Cf || g.ldcf % 4 || !aligned16(g.Cf) || g.slab % 4) return -1;
   } else {
