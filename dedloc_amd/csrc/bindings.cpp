@@ -165,7 +165,7 @@ void lamb_step(at::Tensor p, const at::Tensor& g, at::Tensor m, at::Tensor v, co
   expect(g, at::kFloat, "g");
   check(dl_lamb_step(f32(p), f32(g), f32(m), f32(v), chunk_tensor.data_ptr<int>(), chunk_start.data_ptr<long>(),
                      chunk_len.data_ptr<int>(), (int)chunk_tensor.numel(), f32(tensor_wd), f32(norms),
-                     (int)tensor_wd.numel(), (float)beta1, (float)beta2, (float)eps, (float)step_size,
+                     (int)tensor_wd.numel(), beta1, beta2, (float)eps, (float)step_size,
                      (float)clamp_value, (float)grad_scale, nullptr, cur_stream(p)),
         "lamb_step");
 }
@@ -334,8 +334,17 @@ void embed_bwd(const at::Tensor& ds, const at::Tensor& ids, const c10::optional<
                at::Tensor dpemb, at::Tensor dtemb, int64_t S) {
   expect(ds, at::kBFloat16, "ds");
   for (auto* t : {&dwemb, &dpemb, &dtemb}) expect(*t, at::kFloat, "embedding grad");
+  expect(ids, at::kLong, "ids");
   const int64_t T = ids.numel(), E = ds.size(-1);
-  const long* ttp = tt.has_value() ? tt->data_ptr<long>() : nullptr;
+  // the kernels run B = T / S whole sequences: a partial one would silently lose its rows
+  TORCH_CHECK(S > 0 && T % S == 0, "embed_bwd: ", T, " ids are not a whole number of sequences of S = ", S);
+  TORCH_CHECK(ds.numel() == T * E, "embed_bwd: ds has ", ds.numel(), " elements, expected ", T, " ids x E = ", E);
+  const long* ttp = nullptr;
+  if (tt.has_value()) {
+    expect(*tt, at::kLong, "token_type_ids");
+    TORCH_CHECK(tt->numel() == T, "embed_bwd: one token type per id");
+    ttp = tt->data_ptr<long>();
+  }
   check(dl_embed_bwd(cbf(ds), ids.data_ptr<long>(), ttp, f32(dwemb), f32(dpemb), f32(dtemb), (int)(T / S), (int)S,
                      (int)E, (int)dtemb.size(0), cur_stream(ds)),
         "embed_bwd");

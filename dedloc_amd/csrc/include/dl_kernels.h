@@ -31,8 +31,8 @@ int dl_add_bf16_to_f32(const bf16_t* x, float* y, size_t n, float alpha, hipStre
 
 // optim.hip
 int dl_lamb_step(float* p, const float* g, float* m, float* v, const int* chunk_tensor, const long* chunk_start,
-                 const int* chunk_len, int nchunks, const float* tensor_wd, float* norms, int ntensors, float beta1,
-                 float beta2, float eps, float step_size, float clamp_value, float grad_scale, float* trust_out,
+                 const int* chunk_len, int nchunks, const float* tensor_wd, float* norms, int ntensors, double beta1,
+                 double beta2, float eps, float step_size, float clamp_value, float grad_scale, float* trust_out,
                  hipStream_t st);
 int dl_larc_sgd_step(float* p, const float* g, float* buf, const int* chunk_tensor, const long* chunk_start,
                      const int* chunk_len, int nchunks, const float* tensor_wd, float* norms, int ntensors, float lr,

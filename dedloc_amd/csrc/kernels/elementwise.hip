@@ -64,7 +64,9 @@ __global__ __launch_bounds__(256) void gelu_bwd_kernel(const bf16_t* __restrict_
     load_bf16<8>(dy + i * 8, g);
     load_bf16<8>(h + i * 8, v);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] *= gelu_tanh_grad(v[j]);
+    // the sigmoid form: 1 + tanh(u) cancels in fp32 from x = -3.5 down (tanh rounds to -1), where the
+    // tanh form returns a derivative of 0 or twice the true one
+    for (int j = 0; j < 8; ++j) g[j] *= gelu_tanh_grad_sig(v[j]);
     store_bf16<8>(dh + i * 8, g);
   }
 }

@@ -23,7 +23,8 @@ __global__ __launch_bounds__(kBlock) void lamb_phase1(float* __restrict__ p, con
                                                       const int* __restrict__ chunk_tensor, const long* __restrict__ chunk_start,
                                                       const int* __restrict__ chunk_len, const float* __restrict__ tensor_wd,
                                                       float* __restrict__ norms,  // [T][2]: ||p||^2, ||u||^2
-                                                      float beta1, float beta2, float eps, float grad_scale) {
+                                                      float beta1, float beta2, float omb1, float omb2, float eps,
+                                                      float grad_scale) {
   __shared__ float scratch[16];
   const int c = blockIdx.x;
   const int t = chunk_tensor[c];
@@ -34,8 +35,8 @@ __global__ __launch_bounds__(kBlock) void lamb_phase1(float* __restrict__ p, con
   for (int i = threadIdx.x; i < len; i += blockDim.x) {
     const long k = s0 + i;
     const float gi = g[k] * grad_scale;
-    const float mi = beta1 * m[k] + (1.f - beta1) * gi;
-    const float vi = beta2 * v[k] + (1.f - beta2) * gi * gi;
+    const float mi = beta1 * m[k] + omb1 * gi;
+    const float vi = beta2 * v[k] + omb2 * gi * gi;
     m[k] = mi;
     v[k] = vi;
     const float pi = p[k];
@@ -237,12 +238,15 @@ inline int grid_for(size_t n) {
 }  // namespace
 
 int dl_lamb_step(float* p, const float* g, float* m, float* v, const int* chunk_tensor, const long* chunk_start,
-                 const int* chunk_len, int nchunks, const float* tensor_wd, float* norms, int ntensors, float beta1,
-                 float beta2, float eps, float step_size, float clamp_value, float grad_scale, float* trust_out,
+                 const int* chunk_len, int nchunks, const float* tensor_wd, float* norms, int ntensors, double beta1,
+                 double beta2, float eps, float step_size, float clamp_value, float grad_scale, float* trust_out,
                  hipStream_t st) {
   DL_HIP_CHECK(hipMemsetAsync(norms, 0, sizeof(float) * 2 * ntensors, st));
-  lamb_phase1<<<nchunks, kBlock, 0, st>>>(p, g, m, v, chunk_tensor, chunk_start, chunk_len, tensor_wd, norms, beta1,
-                                          beta2, eps, grad_scale);
+  // 1 - beta from the unrounded beta, as the reference optimizer forms it: 1.f - (float)0.999 is off
+  // from 0.001 by 1.3e-5 relative, and with it the whole second moment after the first step
+  lamb_phase1<<<nchunks, kBlock, 0, st>>>(p, g, m, v, chunk_tensor, chunk_start, chunk_len, tensor_wd, norms,
+                                          (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps,
+                                          grad_scale);
   lamb_phase2<<<nchunks, kBlock, 0, st>>>(p, m, v, chunk_tensor, chunk_start, chunk_len, tensor_wd, norms, step_size,
                                           eps, clamp_value, trust_out);
   return 0;

@@ -202,9 +202,10 @@ def _gelu_fwd_cpu(h):
 def _gelu_bwd_cpu(dy, h, dbias=None):
     x = h.float()
     k0, k1 = math.sqrt(2.0 / math.pi), 0.044715
-    u = k0 * (x + k1 * x ** 3)
-    t = torch.tanh(u)
-    d = 0.5 * (1 + t) + 0.5 * x * (1 - t * t) * k0 * (1 + 3 * k1 * x * x)
+    # gelu_new(x) = x sigmoid(2u): d = s + 2 x s (1 - s) u'.  (The tanh form's 1 + tanh(u) cancels in
+    # fp32 for x below about -3.5.)
+    s = torch.sigmoid(2 * k0 * (x + k1 * x ** 3))
+    d = s + 2 * x * (s * (1 - s)) * (k0 * (1 + 3 * k1 * x * x))
     dh = _bf(dy.float() * d)
     if dbias is not None:
         dbias.add_(dh.float().reshape(-1, dh.shape[-1]).sum(0))
@@ -458,8 +459,12 @@ def _embed_fwd_cpu(ids, tt, wemb, pemb, temb, gamma, beta, S, eps):
 
 @_impl("embed_bwd")
 def _embed_bwd_cpu(ds, ids, tt, dwemb, dpemb, dtemb, S):
-    g = ds.float().reshape(-1, ds.shape[-1])
-    T = g.shape[0]
+    T, E = ids.numel(), ds.shape[-1]
+    if S <= 0 or T % S != 0:
+        raise RuntimeError(f"embed_bwd: {T} ids are not a whole number of sequences of S = {S}")
+    if ds.numel() != T * E:
+        raise RuntimeError(f"embed_bwd: ds has {ds.numel()} elements, expected {T} ids x E = {E}")
+    g = ds.float().reshape(-1, E)
     dwemb.index_add_(0, ids.reshape(-1), g)
     pos = torch.arange(T) % S
     dpemb.index_add_(0, pos, g)
