@@ -67,7 +67,8 @@ def build(verbose: bool = False, jobs: int | None = None) -> str:
     for src in hip_srcs:
         obj = os.path.join(BUILD, os.path.basename(src).replace(".hip", ".o"))
         objs.append(obj)
-        if _newer(obj, [src] + headers + [__file__]):
+        included = [os.path.join(CSRC, "kernels", f) for f in HIP_INCLUDES.get(os.path.basename(src), [])]
+        if _newer(obj, [src] + included + headers + [__file__]):
             jobs_list.append(["hipcc", *hip_flags, *FILE_FLAGS.get(os.path.basename(src), []), *inc, "-c", src,
                               "-o", obj])
 
@@ -123,6 +124,8 @@ HIP_FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-munsafe-fp-at
 # later subtractions (avg - v_k), which then see the exact product, and identical rows no longer
 # give zero deltas.
 FILE_FLAGS: dict = {"comm_q8.hip": ["-ffp-contract=on"]}
+# kernel files that include another kernel file (for its templates): rebuilt when that one changes
+HIP_INCLUDES: dict = {"attention_compact_q.hip": ["attention.hip"]}
 
 
 def _link(objs, out, tlib, verbose):

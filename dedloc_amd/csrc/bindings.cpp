@@ -537,6 +537,88 @@ at::Tensor attn_bwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& mbia
   return dqkv;
 }
 
+// Compact queries: q [B*Sq, H*64] holds sequence b's queries in the first qcnt[b] rows of its slot of
+// Sq rows; kv [B*S, 2*H*64] (K | V) may be a column slice of the fused QKV buffer (any row stride).
+struct CompactLayout {
+  int64_t B, Sq, D, ld;
+};
+inline CompactLayout compact_layout(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt, int64_t H,
+                                    int64_t S, const char* what) {
+  expect(q, at::kBFloat16, "q");
+  expect(qcnt, at::kInt, "qcnt");
+  TORCH_CHECK(kv.is_cuda() && kv.scalar_type() == at::kBFloat16 && kv.dim() == 2 && kv.stride(1) == 1, what,
+              ": kv must be a 2-D bf16 GPU tensor with unit column stride");
+  TORCH_CHECK(H >= 1 && S >= 64 && S % 64 == 0, what, ": S = ", S, " must be a positive multiple of 64");
+  const int64_t T = kv.size(0), B = T / S, D = kv.size(1) / (2 * H), ld = kv.stride(0);
+  TORCH_CHECK(D == 64 && kv.size(1) == 2 * H * D, "dedloc_amd: ", what, ": compact queries exist for head_dim 64 only (kv has ",
+              kv.size(1), " columns for ", H, " heads)");
+  TORCH_CHECK(B >= 1 && B * S == T, what, ": kv must have B*S rows");
+  TORCH_CHECK(ld >= 2 * H * D && ld % 8 == 0 && reinterpret_cast<uintptr_t>(kv.data_ptr()) % 16 == 0, what,
+              ": kv rows must be 16-byte aligned");
+  TORCH_CHECK(q.dim() == 2 && q.size(1) == H * D && q.size(0) % B == 0, what, ": q must be [B*Sq, H*D]");
+  const int64_t Sq = q.size(0) / B;
+  TORCH_CHECK(Sq >= 64 && Sq % 64 == 0 && Sq <= S, what, ": the query slot Sq = ", Sq,
+              " must be a multiple of 64 in 64 .. S = ", S);
+  TORCH_CHECK(qcnt.numel() == B, what, ": qcnt must be int32[B]");
+  return CompactLayout{B, Sq, D, ld};
+}
+
+std::tuple<at::Tensor, at::Tensor> attn_fwd_q(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt,
+                                              const c10::optional<at::Tensor>& mbias, int64_t H, int64_t S,
+                                              double scale, const c10::optional<at::Tensor>& kvinfo) {
+  const CompactLayout L = compact_layout(q, kv, qcnt, H, S, "attn_fwd_q");
+  auto out = at::empty({L.B * L.Sq, H * L.D}, q.options());
+  auto lse = at::empty({L.B, H, L.Sq}, q.options().dtype(at::kFloat));
+  const float* mb = nullptr;
+  if (mbias.has_value()) {
+    expect(*mbias, at::kFloat, "mbias");
+    TORCH_CHECK(mbias->numel() == L.B * S, "attn_fwd_q: mbias must be [B, S]");
+    mb = f32(*mbias);
+  }
+  check(dl_attn_fwd_q(cbf(q), reinterpret_cast<const bf16_t*>(kv.data_ptr()), L.ld, mb, kvinfo_ptr(kvinfo, L.B),
+                      qcnt.data_ptr<int>(), bf(out), H * L.D, f32(lse), (int)L.B, (int)H, (int)S, (int)L.Sq, (int)L.D,
+                      (float)scale, cur_stream(q)),
+        "attn_fwd_q");
+  return {out, lse};
+}
+
+// returns (dq [B*Sq, H*D], dkv [B*S, 2*H*D], delta [B, H, Sq]); past qcnt[b] dq rows are zero and
+// delta entries are not written
+std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd_q(const at::Tensor& q, const at::Tensor& kv,
+                                                          const at::Tensor& qcnt,
+                                                          const c10::optional<at::Tensor>& mbias,
+                                                          const at::Tensor& out, const at::Tensor& dout,
+                                                          const at::Tensor& lse, int64_t H, int64_t S, double scale,
+                                                          const c10::optional<at::Tensor>& kvinfo,
+                                                          const c10::optional<at::Tensor>& dbias) {
+  const CompactLayout L = compact_layout(q, kv, qcnt, H, S, "attn_bwd_q");
+  expect(out, at::kBFloat16, "out");
+  expect(dout, at::kBFloat16, "dout");
+  expect(lse, at::kFloat, "lse");
+  TORCH_CHECK(out.numel() == q.numel() && dout.numel() == q.numel() && lse.numel() == L.B * H * L.Sq,
+              "attn_bwd_q: out / dout must be [B*Sq, H*D] and lse [B, H, Sq]");
+  auto dq = at::empty_like(q);
+  auto dkv = at::empty({L.B * S, 2 * H * L.D}, q.options());
+  auto delta = at::empty({L.B, H, L.Sq}, q.options().dtype(at::kFloat));
+  const float* mb = nullptr;
+  if (mbias.has_value()) {
+    expect(*mbias, at::kFloat, "mbias");
+    TORCH_CHECK(mbias->numel() == L.B * S, "attn_bwd_q: mbias must be [B, S]");
+    mb = f32(*mbias);
+  }
+  float* dbp = nullptr;
+  if (dbias.has_value()) {
+    expect(*dbias, at::kFloat, "dbias");
+    TORCH_CHECK(dbias->numel() == 3 * H * L.D, "dbias must have 3*H*D elements");
+    dbp = f32(*dbias);
+  }
+  check(dl_attn_bwd_q(cbf(q), reinterpret_cast<const bf16_t*>(kv.data_ptr()), L.ld, mb, kvinfo_ptr(kvinfo, L.B),
+                      qcnt.data_ptr<int>(), cbf(out), cbf(dout), H * L.D, f32(lse), f32(delta), bf(dq), bf(dkv), dbp,
+                      (int)L.B, (int)H, (int)S, (int)L.Sq, (int)L.D, (float)scale, cur_stream(q)),
+        "attn_bwd_q");
+  return {dq, dkv, delta};
+}
+
 // Packed variable-length batches.  seqinfo (device) = int32[2B + 1]: B + 1 row offsets, then B key
 // lengths; seqinfo_host is the same array in host memory — the layout contract is checked on it, so
 // a call costs no device synchronisation, and the largest slot (the grids' x extent) is read from it.
@@ -1909,6 +1991,8 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("knn_vote", &knn_vote);
   m.impl("attn_fwd", &attn_fwd);
   m.impl("attn_bwd", &attn_bwd);
+  m.impl("attn_fwd_q", &attn_fwd_q);
+  m.impl("attn_bwd_q", &attn_bwd_q);
   m.impl("attn_varlen_fwd", &attn_varlen_fwd);
   m.impl("attn_varlen_bwd", &attn_varlen_bwd);
   m.impl("embed_ln_pos_fwd", &embed_ln_pos_fwd);

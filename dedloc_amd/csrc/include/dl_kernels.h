@@ -260,6 +260,17 @@ int dl_attn_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinf
 int dl_attn_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, const bf16_t* out,
                 const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int H,
                 int S, int D, float scale, hipStream_t st);
+// Compact queries (head_dim 64, fixed-S layout): sequence b's queries are the first qcnt[b] rows of its
+// slot of Sq rows (Sq % 64 == 0, 64 <= Sq <= S) in q [B*Sq, ldo]; out / dout / dq share that layout,
+// lse / delta are [B, H, Sq].  kv points at K's first column in the [B*S, ld] key / value buffer (V
+// starts H*64 columns after it); dkv is [B*S, 2*H*64] (dK | dV, all keys).  Slot rows past qcnt[b]
+// are dead: clamped on load, absent from lse / delta, dK / dV and the bias gradients, and stored as
+// zeros in out / dq.  -1 for any other D.
+int dl_attn_fwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
+                  bf16_t* out, long ldo, float* lse, int B, int H, int S, int Sq, int D, float scale, hipStream_t st);
+int dl_attn_bwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
+                  const bf16_t* out, const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dq,
+                  bf16_t* dkv, float* dbias, int B, int H, int S, int Sq, int D, float scale, hipStream_t st);
 // Packed variable-length batches: seqinfo = int32[2B + 1] = B + 1 row offsets (multiples of 64,
 // seqinfo[B] == T) then B key lengths (1 <= len <= slot); lse / delta are [H, T]; max_slot is the
 // largest slot (it sizes the grids).  Same kernels as above, compiled with the packed row mapping.

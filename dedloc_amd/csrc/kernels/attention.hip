@@ -233,31 +233,104 @@ __device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int
   }
 }
 
+// Compact queries (CQ instantiations): the queries of sequence b are the first cnt[b] rows of its
+// slot of Sq rows (Sq % 64 == 0, Sq <= S) in q [B*Sq, H*64]; out / dout / dq share that layout and
+// row stride (ldo), lse / delta are [B, H, Sq].  Keys and values stay in the token buffer: the
+// kernels' qkv argument then points at K's first column (V is H*64 columns further on), and dK / dV
+// go to dkv [B*S, 2*H*64] (dK | dV, row stride lddkv).  Slot rows past cnt[b] are dead, as rows
+// past S are to the other forms: clamped loads, nothing written to lse / delta, no part in dK / dV
+// or the bias gradients.  Their out / dq rows are stored as zeros, not skipped: the compact buffers
+// go on into GEMMs (weight gradients sum over their rows), where unwritten memory must not appear.
+// The CQ instantiations take it as one more kernel argument (a parameter pack that is empty in the
+// other instantiations, so those keep their argument layout and their code).
+struct CompactQ {
+  const bf16_t* q;
+  bf16_t* dq;
+  bf16_t* dkv;
+  long lddkv;
+  const int* cnt;
+  int Sq;
+};
+struct NoCompactQ {};
+template <bool CQ>
+using CompactArg = std::conditional_t<CQ, CompactQ, NoCompactQ>;
+__device__ __forceinline__ NoCompactQ compact_arg() { return {}; }
+__device__ __forceinline__ const CompactQ& compact_arg(const CompactQ& cq) { return cq; }
+// first lse / delta element of (sequence b, head h) for the query rows
+template <bool VARLEN, bool CQ>
+__device__ __forceinline__ long q_stat(const CompactArg<CQ>& cq, int b, int h, int H, int S, int T, long rb) {
+  if constexpr (CQ) return ((long)b * H + h) * cq.Sq;
+  else return seq_stat<VARLEN>(b, h, H, S, T, rb);
+}
+// first row of sequence b's queries / outputs, the rows its query tiles may address, and head h's
+// first query element
+template <bool CQ>
+__device__ __forceinline__ long q_first(const CompactArg<CQ>& cq, int b, long rb) {
+  if constexpr (CQ) return (long)b * cq.Sq;
+  else return rb;
+}
+template <bool CQ>
+__device__ __forceinline__ int q_slot(const CompactArg<CQ>& cq, int S) {
+  if constexpr (CQ) return cq.Sq;
+  else return S;
+}
+template <bool CQ>
+__device__ __forceinline__ const bf16_t* q_head(const CompactArg<CQ>& cq, const bf16_t* qkv, long ld, long ldo, long rb,
+                                                 long qb, int h) {
+  if constexpr (CQ) return cq.q + qb * ldo + h * 64;
+  else return qkv + rb * ld + h * 64;
+}
+// 64 columns of up to blockDim.x rows of a [., ld] bf16 buffer <- 0, one row per thread
+__device__ __forceinline__ void zero_rows64(bf16_t* g, long ld, int rows) {
+  if ((int)threadIdx.x < rows) {
+    uint4* p = reinterpret_cast<uint4*>(g + (long)threadIdx.x * ld);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) p[i] = make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+// live query rows of sequence b: the slot's count (CQ), else the sequence's rows
+template <bool CQ>
+__device__ __forceinline__ int q_rows(const CompactArg<CQ>& cq, int b, int S) {
+  if constexpr (CQ) return max(1, min(cq.cnt[b], cq.Sq));
+  else return S;
+}
+
 // Block = NW waves x QS x 32 query rows of one (batch, head).  NW = 8 (ring only): one 512-query
 // block per head at S = 512, so K / V are staged once per head, and each SIMD's two waves belong
 // to one block.
 // VARLEN: the packed layout (seq_rows .. seq_stat in dl_attn_tile.h): kvinfo is seqinfo, S_ is T, the grid's x
 // extent covers the largest slot and a block past its own slot leaves before any DMA or barrier.
-template <bool RING, int QS, int NW = 4, bool VARLEN = false>
+template <bool RING, int QS, int NW = 4, bool VARLEN = false, typename... CQA>
 __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                           const float* __restrict__ mbias,
                                                           const int* __restrict__ kvinfo, bf16_t* __restrict__ out,
                                                           long ldo, float* __restrict__ lse, int B, int H, int S_,
-                                                          float sl2, int xcd) {
+                                                          float sl2, int xcd, CQA... cqa) {
+  constexpr bool CQ = sizeof...(CQA) == 1;
+  const CompactArg<CQ> cq = compact_arg(cqa...);
   __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 2 * 64 * 4];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int S = seq_rows<VARLEN>(kvinfo, b, S_);
-  if constexpr (VARLEN) {
-    if (bid.x * (32 * QS * NW) >= S) return;  // uniform over the block
+  const int nq = q_rows<CQ>(cq, b, S);
+  if constexpr (VARLEN || CQ) {
+    if (bid.x * (32 * QS * NW) >= nq) {  // uniform over the block
+      if constexpr (CQ) {  // a block of dead rows: zeros
+        const int q0 = bid.x * (32 * QS * NW);
+        zero_rows64(out + ((long)b * cq.Sq + q0) * ldo + h * HD, ldo, cq.Sq - q0);
+      }
+      return;
+    }
   }
   const long rb = seq_base<VARLEN>(kvinfo, b, S);
-  const bf16_t* Qg = qkv + rb * ld + h * HD;
+  const long qb = q_first<CQ>(cq, b, rb);
+  const long ldq = CQ ? ldo : ld;
+  const bf16_t* Qg = q_head<CQ>(cq, qkv, ld, ldo, rb, qb, h);
   bool use_len;
   FwdCtx c;
-  c.Kg = qkv + rb * ld + (long)H * HD + h * HD;
-  c.Vg = qkv + rb * ld + 2L * H * HD + h * HD;
+  c.Kg = qkv + rb * ld + (CQ ? 0L : (long)H * HD) + h * HD;
+  c.Vg = qkv + rb * ld + (CQ ? (long)H * HD : 2L * H * HD) + h * HD;
   c.ld = ld;
   c.S = S;
   c.kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
@@ -278,9 +351,9 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
     q[u] = bid.x * (32 * QS * NW) + w * (32 * QS) + 32 * u + r;
-    const int qc = min(q[u], S - 1);
+    const int qc = min(q[u], nq - 1);
 #pragma unroll
-    for (int ks = 0; ks < 4; ++ks) qf[u][ks] = gload8(Qg + (long)qc * ld + ks * 16 + 8 * hh);
+    for (int ks = 0; ks < 4; ++ks) qf[u][ks] = gload8(Qg + (long)qc * ldq + ks * 16 + 8 * hh);
     if constexpr (RING) {
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) settle(qf[u][ks]);
@@ -319,9 +392,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
 
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
-    const bool live = q[u] < S;
-    store_row64(out + (rb + q[u]) * ldo + h * HD, o[u], 1.f / l[u], hh, live);
-    if (live && hh == 0) lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + q[u]] = m[u] + log2f(l[u]);
+    const bool live = q[u] < nq;
+    if constexpr (CQ)  // dead rows of the slot: zeros (o is finite there, it comes from a clamped live row)
+      store_row64(out + (qb + q[u]) * ldo + h * HD, o[u], live ? 1.f / l[u] : 0.f, hh, q[u] < cq.Sq);
+    else
+      store_row64(out + (qb + q[u]) * ldo + h * HD, o[u], 1.f / l[u], hh, live);
+    if (live && hh == 0) lse[q_stat<VARLEN, CQ>(cq, b, h, H, S, S_, rb) + q[u]] = m[u] + log2f(l[u]);
   }
 }
 
@@ -329,7 +405,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
 // Also computes delta = rowsum(dO * O) for its queries and publishes it for the dkdv kernel.
 // QS = 32-row query sub-blocks per wave (as in the forward: every K / V fragment read from LDS
 // feeds QS MFMAs, and each wave carries QS independent chains).
-template <bool RING, int QS, bool VARLEN = false>
+template <bool RING, int QS, bool VARLEN = false, typename... CQA>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                              const float* __restrict__ mbias,
                                                              const int* __restrict__ kvinfo,
@@ -337,20 +413,31 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
                                                              long ldo, const float* __restrict__ lse,
                                                              float* __restrict__ delta, bf16_t* __restrict__ dqkv,
                                                              float* __restrict__ dbias, int B, int H, int S_, float sl2,
-                                                             float scale, int xcd) {
+                                                             float scale, int xcd, CQA... cqa) {
+  constexpr bool CQ = sizeof...(CQA) == 1;
+  const CompactArg<CQ> cq = compact_arg(cqa...);
   // tail: mask bias (the epilogue reuses the first 2 KiB for the waves' bias-gradient partials)
   __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 4 * 64 * 4];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int S = seq_rows<VARLEN>(kvinfo, b, S_);
-  if constexpr (VARLEN) {
-    if (bid.x * (128 * QS) >= S) return;  // uniform over the block
+  const int nq = q_rows<CQ>(cq, b, S);
+  if constexpr (VARLEN || CQ) {
+    if (bid.x * (128 * QS) >= nq) {  // uniform over the block
+      if constexpr (CQ) {  // a block of dead rows: zeros
+        const int q0 = bid.x * (128 * QS);
+        zero_rows64(cq.dq + ((long)b * cq.Sq + q0) * ldo + h * HD, ldo, cq.Sq - q0);
+      }
+      return;
+    }
   }
   const long rb = seq_base<VARLEN>(kvinfo, b, S);
-  const bf16_t* Qg = qkv + rb * ld + h * HD;
-  const bf16_t* Kg = qkv + rb * ld + (long)H * HD + h * HD;
-  const bf16_t* Vg = qkv + rb * ld + 2L * H * HD + h * HD;
+  const long qb = q_first<CQ>(cq, b, rb);
+  const long ldq = CQ ? ldo : ld;
+  const bf16_t* Qg = q_head<CQ>(cq, qkv, ld, ldo, rb, qb, h);
+  const bf16_t* Kg = qkv + rb * ld + (CQ ? 0L : (long)H * HD) + h * HD;
+  const bf16_t* Vg = qkv + rb * ld + (CQ ? (long)H * HD : 2L * H * HD) + h * HD;
   bool use_len;
   const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   const float* mb_g = (!use_len && mbias) ? mbias + rb : nullptr;
@@ -372,19 +459,19 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
     q[u] = bid.x * (128 * QS) + w * (32 * QS) + 32 * u + r;
-    const int qc = min(q[u], S - 1);
+    const int qc = min(q[u], nq - 1);
     dl[u] = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      qf[u][ks] = gload8(Qg + (long)qc * ld + ks * 16 + 8 * hh);
-      const long oo = (rb + qc) * ldo + h * HD + ks * 16 + 8 * hh;
+      qf[u][ks] = gload8(Qg + (long)qc * ldq + ks * 16 + 8 * hh);
+      const long oo = (qb + qc) * ldo + h * HD + ks * 16 + 8 * hh;
       df[u][ks] = gload8(dout + oo);
       const bf16x8 of = gload8(out + oo);
 #pragma unroll
       for (int e = 0; e < 8; ++e) dl[u] += (float)df[u][ks][e] * (float)of[e];
     }
     dl[u] += __shfl_xor(dl[u], 32, 64);
-    l2[u] = lse[seq_stat<VARLEN>(b, h, H, S, S_, rb) + qc];
+    l2[u] = lse[q_stat<VARLEN, CQ>(cq, b, h, H, S, S_, rb) + qc];
     if constexpr (RING) {
       settle(l2[u]);
       settle(dl[u]);
@@ -529,9 +616,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
   for (int u = 0; u < QS; ++u) qe[u] = bid.x * (128 * QS) + w_ * (32 * QS) + 32 * u + r_;
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
-    const bool live = qe[u] < S;
-    if (live && hh_ == 0) delta[seq_stat<VARLEN>(b, h, H, S, S_, rb) + qe[u]] = dl[u];
-    store_row64(dqkv + (rb + qe[u]) * ld + h * HD, dq[u], scale, hh_, live);
+    const bool live = qe[u] < nq;
+    if (live && hh_ == 0) delta[q_stat<VARLEN, CQ>(cq, b, h, H, S, S_, rb) + qe[u]] = dl[u];
+    if constexpr (CQ)  // dead rows of the slot: zeros
+      store_row64(cq.dq + (qb + qe[u]) * ldo + h * HD, dq[u], live ? scale : 0.f, hh_, qe[u] < cq.Sq);
+    else
+      store_row64(dqkv + (rb + qe[u]) * ld + h * HD, dq[u], scale, hh_, live);
   }
   if (dbias) {
     // Fused bias gradient of the QKV projection (replaces a [T, 3H*64] column-sum pass):
@@ -552,7 +642,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
       for (int i = 0; i < 16; ++i) {  // dQ column 32 t + 8 (i >> 2) + 4 hh_ + (i & 3), as stored above
         float v = 0.f;
 #pragma unroll
-        for (int u = 0; u < QS; ++u) v += qe[u] < S ? round_bf16(dq[u][t][i] * scale) : 0.f;
+        for (int u = 0; u < QS; ++u) v += qe[u] < nq ? round_bf16(dq[u][t][i] * scale) : 0.f;
         cq[t][i] = half_wave_sum(v);
       }
 #pragma unroll
@@ -561,7 +651,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
       for (int e = 0; e < 8; ++e) {  // dO column 16 ks + 8 hh_ + e, as loaded above
         float v = 0.f;
 #pragma unroll
-        for (int u = 0; u < QS; ++u) v += qe[u] < S ? (float)df[u][ks][e] : 0.f;
+        for (int u = 0; u < QS; ++u) v += qe[u] < nq ? (float)df[u][ks][e] : 0.f;
         cd[ks][e] = half_wave_sum(v);
       }
     if (r_ == 0) {
@@ -592,11 +682,13 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
 // KS = 32-key sub-blocks per wave: with KS = 2 every Q / dO fragment read from LDS feeds two
 // MFMAs; the dK/dV accumulators (128 registers) need the whole 512-entry register file, so that
 // form runs one wave per SIMD (launch bound 256 x 1) and hides latency by ILP instead of waves.
-template <bool RING, int KS, bool VARLEN = false>
+template <bool RING, int KS, bool VARLEN = false, typename... CQA>
 __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ qkv, long ld, const float* __restrict__ mbias, const int* __restrict__ kvinfo,
     const bf16_t* __restrict__ dout, long ldo, const float* __restrict__ lse, const float* __restrict__ delta,
-    bf16_t* __restrict__ dqkv, int B, int H, int S_, float sl2, float scale, int xcd) {
+    bf16_t* __restrict__ dqkv, int B, int H, int S_, float sl2, float scale, int xcd, CQA... cqa) {
+  constexpr bool CQ = sizeof...(CQA) == 1;
+  const CompactArg<CQ> cq = compact_arg(cqa...);
   __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 2 * 2 * 64 * 4];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
@@ -606,12 +698,25 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
     if (bid.x * (128 * KS) >= S) return;  // uniform over the block
   }
   const long rb = seq_base<VARLEN>(kvinfo, b, S);
-  const bf16_t* Qg = qkv + rb * ld + h * HD;
-  const bf16_t* Kg = qkv + rb * ld + (long)H * HD + h * HD;
-  const bf16_t* Vg = qkv + rb * ld + 2L * H * HD + h * HD;
-  const bf16_t* dOg = dout + rb * ldo + h * HD;
-  const float* lse_g = lse + seq_stat<VARLEN>(b, h, H, S, S_, rb);
-  const float* del_g = delta + seq_stat<VARLEN>(b, h, H, S, S_, rb);
+  const int nq = q_rows<CQ>(cq, b, S);
+  const long qb = q_first<CQ>(cq, b, rb);
+  const long ldq = CQ ? ldo : ld;
+  const bf16_t* Qg = q_head<CQ>(cq, qkv, ld, ldo, rb, qb, h);
+  const bf16_t* Kg = qkv + rb * ld + (CQ ? 0L : (long)H * HD) + h * HD;
+  const bf16_t* Vg = qkv + rb * ld + (CQ ? (long)H * HD : 2L * H * HD) + h * HD;
+  const bf16_t* dOg = dout + qb * ldo + h * HD;
+  const float* lse_g = lse + q_stat<VARLEN, CQ>(cq, b, h, H, S, S_, rb);
+  const float* del_g = delta + q_stat<VARLEN, CQ>(cq, b, h, H, S, S_, rb);
+  // dK / dV of this head go to thirds 2 and 3 of dqkv, or (CQ) to the two halves of cq.dkv
+  bf16_t* dkv_g;
+  long ldd;
+  if constexpr (CQ) {
+    dkv_g = cq.dkv - (long)H * HD;  // so that dK sits H*HD columns in, as in dqkv
+    ldd = cq.lddkv;
+  } else {
+    dkv_g = dqkv;
+    ldd = ld;
+  }
   float* rowv = reinterpret_cast<float*>(smem + 4 * TILE_BYTES);  // [2 buf][lse 64 | delta 64]
 
   int k[KS];
@@ -623,8 +728,8 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
 #pragma unroll
     for (int u = 0; u < KS; ++u) {
       if (k[u] < S) {
-        bf16_t* dkp = dqkv + (rb + k[u]) * ld + (long)H * HD + h * HD;
-        bf16_t* dvp = dqkv + (rb + k[u]) * ld + 2L * H * HD + h * HD;
+        bf16_t* dkp = dkv_g + (rb + k[u]) * ldd + (long)H * HD + h * HD;
+        bf16_t* dvp = dkv_g + (rb + k[u]) * ldd + 2L * H * HD + h * HD;
 #pragma unroll
         for (int v = 0; v < 8; ++v) {  // the same 64 columns the regular epilogue covers (32t + 8v' + 4hh)
           store4(dkp + 8 * v + 4 * hh, 0.f, 0.f, 0.f, 0.f);
@@ -634,10 +739,11 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
     }
     return;
   }
-  const int nt = S / 64;
+  // query tiles: all of the sequence's, or (CQ) the slot's tiles that hold a live row
+  const int nt = CQ ? (nq + 63) / 64 : S / 64;
   auto issue = [&](int st) {  // RING: query tile st -> slot st % NBUF; waves 0-1 fetch lse, 2-3 delta
     uint8_t* slot = smem + (st % NBUF) * STAGE;
-    dma_tile(Qg, ld, st * 64, slot, w, lane);
+    dma_tile(Qg, ldq, st * 64, slot, w, lane);
     dma_tile(dOg, ldo, st * 64, slot + TILE_BYTES, w, lane);
     dma_f32x64((w < 2 ? lse_g : del_g) + st * 64, slot + 2 * TILE_BYTES + (w < 2 ? 0 : 256), lane);
   };
@@ -678,8 +784,8 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
   if constexpr (RING) {
     wait_vm_all();
   } else {
-    tile_load(qr, Qg, ld, 0, S);
-    tile_load(dr, dOg, ldo, 0, S);
+    tile_load(qr, Qg, ldq, 0, q_slot<CQ>(cq, S));
+    tile_load(dr, dOg, ldo, 0, q_slot<CQ>(cq, S));
     if (threadIdx.x < 128) rv = threadIdx.x < 64 ? lse_g[threadIdx.x] : del_g[threadIdx.x - 64];
     tile_store(qr, smem);
     tile_store(dr, smem + TILE_BYTES);
@@ -706,14 +812,26 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
       Qs = smem + (qt & 1) * 2 * TILE_BYTES;
       lse_s = rowv + (qt & 1) * 128;
       if (qt + 1 < nt) {
-        tile_load(qr, Qg, ld, (qt + 1) * 64, S);
-        tile_load(dr, dOg, ldo, (qt + 1) * 64, S);
+        tile_load(qr, Qg, ldq, (qt + 1) * 64, q_slot<CQ>(cq, S));
+        tile_load(dr, dOg, ldo, (qt + 1) * 64, q_slot<CQ>(cq, S));
         if (threadIdx.x < 128)
           rv = threadIdx.x < 64 ? lse_g[(qt + 1) * 64 + threadIdx.x] : del_g[(qt + 1) * 64 + threadIdx.x - 64];
       }
     }
     const uint8_t* Ds = Qs + TILE_BYTES;
     const float* del_s = lse_s + 64;
+    if constexpr (CQ) {
+      // The slot's last live tile may end in dead rows, whose lse / delta were never written: give
+      // them lse = +1e30 (P = exp2(s - 1e30) = 0, so dV and dS get nothing from them) and delta = 0.
+      // The tile has landed and no later stage overwrites it (it is the loop's last).
+      if (qt == nt - 1 && (nq & 63) != 0) {  // uniform over the block
+        if (threadIdx.x < 64 && qt * 64 + (int)threadIdx.x >= nq) {
+          const_cast<float*>(lse_s)[threadIdx.x] = -NEG_BIG;
+          const_cast<float*>(del_s)[threadIdx.x] = 0.f;
+        }
+        __syncthreads();
+      }
+    }
 #pragma unroll
     for (int i2 = 0; i2 < 2; ++i2) {
       floatx16 sc[KS], dp[KS];
@@ -788,8 +906,8 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
 #pragma unroll
   for (int u = 0; u < KS; ++u) {
     const bool live = k[u] < S;
-    store_row64(dqkv + (rb + k[u]) * ld + (long)H * HD + h * HD, dk[u], scale, hh, live);
-    store_row64(dqkv + (rb + k[u]) * ld + 2L * H * HD + h * HD, dv[u], 1.f, hh, live);
+    store_row64(dkv_g + (rb + k[u]) * ldd + (long)H * HD + h * HD, dk[u], scale, hh, live);
+    store_row64(dkv_g + (rb + k[u]) * ldd + 2L * H * HD + h * HD, dv[u], 1.f, hh, live);
   }
 }
 
@@ -798,6 +916,14 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
 constexpr int kAttnXcd = 1;
 
 }  // namespace
+
+// The compact-query instantiations and their entry points are compiled in a translation unit of
+// their own (attention_compact_q.hip, which includes this file for the kernel templates), so that
+// this unit's code object holds exactly the kernels it held before, at the same addresses: the lean
+// forward loop's row maximum (vmax3) reads the score accumulators right behind the MFMA chain, what
+// it sees depends on instruction timing, and moving a kernel inside its code object was measured to
+// change output bits (tests/test_attention_varlen_gpu.py, packed against fixed-S).
+#ifndef DL_ATTN_COMPACT_Q_UNIT
 
 int dl_attn_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo, float* lse,
                 int B, int H, int S, int D, float scale, hipStream_t st) {
@@ -862,3 +988,42 @@ int dl_attn_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf1
                                                                B, H, T, sl2, scale, kAttnXcd);
   return 0;
 }
+
+#else  // DL_ATTN_COMPACT_Q_UNIT
+
+// Compact queries (struct CompactQ above): q / out / dout / dq [B*Sq, H*64], qcnt int32[B], lse /
+// delta [B, H, Sq]; kv points at K's first column of the [B*S, ld] key / value buffer (V follows H*64
+// columns later); dkv [B*S, 2*H*64].  Head_dim 64 and the fixed-S layout only.
+static bool compact_q_ok(const void* q, const void* kv, const int* qcnt, int B, int H, int S, int Sq, int D, long ld,
+                         long ldo) {
+  return q && kv && qcnt && B >= 1 && H >= 1 && D == HD && S % 64 == 0 && Sq % 64 == 0 && Sq >= 64 && Sq <= S &&
+         ld % 8 == 0 && ld >= 2L * H * HD && ldo % 8 == 0 && ldo >= (long)H * HD;
+}
+
+int dl_attn_fwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
+                  bf16_t* out, long ldo, float* lse, int B, int H, int S, int Sq, int D, float scale, hipStream_t st) {
+  if (!compact_q_ok(q, kv, qcnt, B, H, S, Sq, D, ld, ldo)) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  const CompactQ cq{q, nullptr, nullptr, 0, qcnt, Sq};
+  dim3 grid((Sq + 255) / 256, H, B);
+  attn_fwd_kernel<true, 2, 4, false, CompactQ><<<grid, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, sl2,
+                                                                 kAttnXcd, cq);
+  return 0;
+}
+
+int dl_attn_bwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
+                  const bf16_t* out, const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dq,
+                  bf16_t* dkv, float* dbias, int B, int H, int S, int Sq, int D, float scale, hipStream_t st) {
+  if (!compact_q_ok(q, kv, qcnt, B, H, S, Sq, D, ld, ldo) || !dq || !dkv) return -1;
+  const float sl2 = scale * 1.4426950408889634f;
+  const CompactQ cq{q, dq, dkv, 2L * H * HD, qcnt, Sq};
+  dim3 grid_dq((Sq + 255) / 256, H, B);
+  attn_bwd_dq_kernel<true, 2, false, CompactQ><<<grid_dq, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, dout, ldo, lse, delta,
+                                                                    nullptr, dbias, B, H, S, sl2, scale, kAttnXcd, cq);
+  dim3 grid_kv((S + 127) / 128, H, B);
+  attn_bwd_dkdv_kernel<true, 1, false, CompactQ><<<grid_kv, 256, 0, st>>>(kv, ld, mbias, kvinfo, dout, ldo, lse, delta,
+                                                                      nullptr, B, H, S, sl2, scale, kAttnXcd, cq);
+  return 0;
+}
+
+#endif  // DL_ATTN_COMPACT_Q_UNIT

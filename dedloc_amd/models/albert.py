@@ -152,6 +152,11 @@ _SHARED_WGRAD = True
 # it shares the forward's exp2 / rcp, and the FFN-down data gradient's epilogue becomes one multiply
 # instead of a second sigmoid evaluation per element (gemm_gelu_d / gemm_dmul, gemm8 DL_EPI_GELUD / DL_EPI_DMUL).
 _GELU_GRAD_IN_FWD = True
+# AlbertForPreTraining reads only the MLM target rows and one [CLS] row per sequence of the last
+# layer's output, so its last layer application runs on those rows alone (K and V still on every
+# row): _AlbertLastLayerFn over ops.attn_fwd_q / attn_bwd_q.  Head_dim 64 on rectangular batches;
+# everything else, and every other model class, runs the full layer.
+_LAST_LAYER_ROWS = True
 
 
 class _AlbertLayerFn(torch.autograd.Function):
@@ -224,6 +229,152 @@ class _AlbertLayerFn(torch.autograd.Function):
         _wgrad(O, dqkv, h, lv, "gwqkv")
         dh = _dgrad(O, dqkv, lv, "wqkv", ds1)
         return dh, None, None, None, None, None
+
+
+class LastLayerRows:
+    """The rows of the last layer's input that the heads read, in the compact layout of
+    ``ops.attn_fwd_q``: sequence b owns a slot of ``Sq`` rows (a multiple of 64) of ``rows`` [B*Sq].
+    Its [CLS] row comes first.  Every other row sits in the half (rows 0-31 or 32-63) of a 64-row
+    tile that it occupies in its own sequence, halves filled in order of appearance: the attention
+    forward gives a query row the same bits wherever it sits only as long as it keeps its 32-row
+    sub-block within the wave, and the heads' inputs then equal the full layer's bit for bit.  (A
+    sequence with more than Sq/2 rows of one half puts the excess into the other half's free places:
+    still the right rows, one rounding step apart.)  Places left free hold the [CLS] row again, a
+    valid index: they get a zero gradient, and past ``qcnt[b]`` (int32[B], one more than the last
+    place in use) they are dead in attention.  ``head_rows`` / ``targets`` are the compact rows under
+    the MLM head and their labels, in the order the full path feeds them to the head.  ``owner``
+    [B*Sq] names, for every place, the first place that holds the same row (itself, unless the row
+    is repeated): the backward folds the gradients of a repeated row into that place."""
+
+    def __init__(self, rows, qcnt, Sq, head_rows, targets, owner):
+        self.rows, self.qcnt, self.Sq, self.head_rows, self.targets = rows, qcnt, Sq, head_rows, targets
+        self.owner = owner
+
+    @staticmethod
+    def _build(b_idx, s_pos, targets, B, Sp, Sq):
+        """b_idx / s_pos [N]: sequence and position of every MLM row, grouped by sequence."""
+        dev = b_idx.device
+        # an entry at position 0 (a target on [CLS], or an unused entry of the fixed-shape form) shares
+        # the [CLS] place: autograd then sums the heads' gradients of that row as it does on the full
+        # output, before the layer's backward
+        cls = s_pos == 0
+        odd = (s_pos // 32) % 2
+        even = (1 - odd) * (~cls).to(odd.dtype)
+        zeros = torch.zeros(B, dtype=torch.long, device=dev)
+        n_odd, n_even = zeros.scatter_add(0, b_idx, odd), zeros.scatter_add(0, b_idx, even)
+        # rank inside (sequence, half): the running count less the count before the sequence; the
+        # [CLS] row holds rank 0 of the even half
+        r_odd = torch.cumsum(odd, 0) - 1 - (torch.cumsum(n_odd, 0) - n_odd)[b_idx]
+        r_even = torch.cumsum(even, 0) - (torch.cumsum(n_even, 0) - n_even)[b_idx]
+        rank = torch.where(odd == 1, r_odd, r_even)
+        cap = Sq // 2
+        fits = rank < cap
+        others = torch.where(odd == 1, (n_even + 1)[b_idx], n_odd[b_idx])  # rows of the other half
+        half = torch.where(fits, odd, even)
+        rank = torch.where(fits, rank, others + rank - cap)
+        place = torch.where(cls, torch.zeros_like(rank), 64 * (rank // 32) + 32 * half + rank % 32)
+        head_rows = b_idx * Sq + place
+        rows = (torch.arange(B, device=dev)[:, None] * Sp).expand(B, Sq).reshape(-1).clone()
+        rows[head_rows] = b_idx * Sp + s_pos
+        qcnt = torch.ones(B, dtype=torch.long, device=dev).scatter_reduce(0, b_idx, place + 1, "amax")
+        places = torch.arange(B * Sq, device=dev)
+        first = torch.full((B * Sp,), B * Sq, dtype=torch.long, device=dev).scatter_reduce(0, rows, places, "amin")
+        return LastLayerRows(rows, qcnt.to(torch.int32), Sq, head_rows, targets, first[rows])
+
+    @staticmethod
+    def from_positions(mlm_positions, mlm_labels, Sp):
+        """Fixed-shape targets [B, P]: every entry gets a place (an unused one points at position 0
+        with label -100 and shares the [CLS] place).  No host synchronisation.  None when the slot would not be smaller than the sequence."""
+        B, P = mlm_positions.shape
+        Sq = (1 + P + 63) // 64 * 64
+        if P == 0 or Sq >= Sp:
+            return None
+        b_idx = torch.arange(B, device=mlm_positions.device).repeat_interleave(P)
+        return LastLayerRows._build(b_idx, mlm_positions.reshape(-1), mlm_labels.reshape(-1), B, Sp, Sq)
+
+    @staticmethod
+    def from_labels(labels, Sp):
+        """HF ``labels`` [B, S] (-100 = ignore).  The per-sequence target counts are read on the host
+        — the one synchronisation this form costs (it replaces that of ``nonzero``) — and size the
+        slot.  None without any target or when the slot would not be smaller than the sequence."""
+        B, S = labels.shape
+        sel = labels != -100
+        host = sel.sum(1).tolist()
+        M, Sq = sum(host), (1 + max(host) + 63) // 64 * 64
+        if M == 0 or Sq >= Sp:
+            return None
+        pos = torch.nonzero_static(sel.reshape(-1), size=M).squeeze(1)  # (b, position) order, no sync
+        return LastLayerRows._build(pos // S, pos % S, labels.reshape(-1)[pos], B, Sp, Sq)
+
+
+class _AlbertLastLayerFn(torch.autograd.Function):
+    """The last application of the shared layer, computed for the rows in ``sel`` (LastLayerRows)
+    only: [B*S, hidden] in, [B*Sq, hidden] out.  K and V are projected for every row, everything
+    else — Q, the attention queries, the output projection, both LayerNorms and the FFN — for the
+    compact rows, forward and backward.  Same kernels and the same hand schedule as _AlbertLayerFn;
+    each live output row equals the full layer's row."""
+
+    @staticmethod
+    def forward(ctx, h, mask, lv, H, S, eps, sel):
+        O = ops.OPS
+        Hd = h.shape[1]
+        mbias, kvinfo = mask
+        scale = 1.0 / math.sqrt(Hd // H)
+        kv = O.gemm(h, lv["wqkv"][Hd:], lv["bqkv32"][Hd:], None, False, True, 0)
+        hq = h.index_select(0, sel.rows)
+        q = O.gemm(hq, lv["wqkv"][:Hd], lv["bqkv32"][:Hd], None, False, True, 0)
+        att, lse = ops.attn_fwd_q(q, kv, sel.qcnt, mbias, H, S, scale, kvinfo)
+        s1 = O.gemm(att, lv["wo"], lv["bo32"], hq, False, True, 0)
+        h1, _, m1, r1 = O.layernorm_fwd(s1, None, lv["ln1g"], lv["ln1b"], eps)
+        f, g = (O.gemm_gelu_d if _GELU_GRAD_IN_FWD else O.gemm_gelu)(h1, lv["w1"], lv["b132"])
+        s2 = O.gemm(g, lv["w2"], lv["b232"], h1, False, True, 0)
+        out, _, m2, r2 = O.layernorm_fwd(s2, None, lv["ln2g"], lv["ln2b"], eps)
+        ctx.save_for_backward(h, hq, q, kv, att, lse, s1, m1, r1, h1, f, g, s2, m2, r2)
+        ctx.lv, ctx.mask, ctx.H, ctx.S, ctx.sel, ctx.scale = lv, mask, H, S, sel, scale
+        ctx.gelu_d = _GELU_GRAD_IN_FWD
+        return out
+
+    @staticmethod
+    def backward(ctx, dy):
+        O = ops.OPS
+        h, hq, q, kv, att, lse, s1, m1, r1, h1, f, g, s2, m2, r2 = ctx.saved_tensors
+        lv, sel = ctx.lv, ctx.sel
+        Hd = h.shape[1]
+        dy = dy.contiguous()
+        # This layer's reduction lengths (B*Sq, and B*S for K/V only) are not the other layers', so it
+        # stays out of their shared slab series: plain fp32 accumulation into the gradient (it is the
+        # first backward call; the layer before it opens the series).
+        ds2 = O.layernorm_bwd(dy, s2, lv["ln2g"], m2, r2, lv["gln2g"], lv["gln2b"], True, lv["gb2"])
+        O.gemm_acc_f32(ds2, g, lv["gw2"], True, False)
+        wt = "w2t" in lv
+        dfn = O.gemm_dmul if ctx.gelu_d else O.gemm_dgelu
+        df = dfn(ds2, lv["w2t"], f, lv["gb1"], True) if wt else dfn(ds2, lv["w2"], f, lv["gb1"])
+        O.gemm_acc_f32(df, h1, lv["gw1"], True, False)
+        dh1 = _dgrad(O, df, lv, "w1", ds2)
+        del df
+        ds1 = O.layernorm_bwd(dh1, s1, lv["ln1g"], m1, r1, lv["gln1g"], lv["gln1b"], True, lv["gbo"])
+        O.gemm_acc_f32(ds1, att, lv["gwo"], True, False)
+        datt = _dgrad(O, ds1, lv, "wo", None)
+        dq, dkv, _ = ops.attn_bwd_q(q, kv, sel.qcnt, ctx.mask[0], att, datt, lse, ctx.H, ctx.S, ctx.scale, ctx.mask[1],
+                                    lv["gbqkv"])
+        O.gemm_acc_f32(dq, hq, lv["gwqkv"][:Hd], True, False)
+        O.gemm_acc_f32(dkv, h, lv["gwqkv"][Hd:], True, False)
+        # Data gradient.  Every row gets its K / V part; a row the heads read gets, as in the full
+        # layer, ds1 + [dQ | dK | dV] Wqkv from ONE GEMM (one rounding to bf16, not the sum of two
+        # rounded parts) and replaces its K / V-only value.  A row held by several places (the
+        # padding repeats the [CLS] row) has their dQ and ds1 folded into its first place, whose
+        # result every one of them writes back: equal values, so the copy is well defined.
+        dqo = torch.zeros_like(dq).index_add_(0, sel.owner, dq)
+        ds1o = torch.zeros_like(ds1).index_add_(0, sel.owner, ds1)
+        dcat = torch.cat([dqo, dkv.index_select(0, sel.rows)], 1)
+        if "wqkvt" in lv:  # transposed copy; its K | V column block serves the rows the heads do not read
+            dhq = O.gemm(dcat, lv["wqkvt"], None, ds1o, False, True, 0)
+            dh = O.gemm(dkv, lv["wqkvt"][:, Hd:], None, None, False, True, 0)
+        else:
+            dhq = O.gemm(dcat, lv["wqkv"], None, ds1o, False, False, 0)
+            dh = O.gemm(dkv, lv["wqkv"][Hd:], None, None, False, False, 0)
+        dh.index_copy_(0, sel.rows, dhq.index_select(0, sel.owner))
+        return dh, None, None, None, None, None, None
 
 
 def _wgrad(O, dy, x, lv, name):
@@ -418,9 +569,19 @@ class AlbertPreTrainedModel(nn.Module):
             gln2g=f.g(pre + "full_layer_layer_norm.weight"), gln2b=f.g(pre + "full_layer_layer_norm.bias"),
         )
 
-    def _albert_layer(self, h, lv, mask, S):
+    def _albert_layer(self, h, lv, mask, S, last_rows=None):
         c = self.config
+        if last_rows is not None:
+            return _AlbertLastLayerFn.apply(h, mask, lv, c.num_attention_heads, S, c.layer_norm_eps, last_rows)
         return _AlbertLayerFn.apply(h, mask, lv, c.num_attention_heads, S, c.layer_norm_eps)
+
+    def last_layer_rows_supported(self) -> bool:
+        """Whether the last layer can run on compact rows (LastLayerRows): the module switch, the
+        residual-in-GEMM layer form the compact layer is written in, one layer per group application
+        and head_dim 64 (the only head size with compact-query attention kernels)."""
+        c = self.config
+        return (_LAST_LAYER_ROWS and _RESIDUAL_IN_GEMM and c.inner_group_num == 1
+                and c.hidden_size == 64 * c.num_attention_heads)
 
     def _packed(self, pack_sequences, input_ids, attention_mask, token_type_ids, lengths, labels=None):
         """The PackedBatch of this call, or None when the call runs on the rectangular layout."""
@@ -431,9 +592,13 @@ class AlbertPreTrainedModel(nn.Module):
             batch["labels"] = labels
         return pack_batch(batch, lengths, self.config.pad_token_id)
 
-    def encode(self, input_ids=None, attention_mask=None, token_type_ids=None, packed: Optional[PackedBatch] = None):
+    def encode(self, input_ids=None, attention_mask=None, token_type_ids=None, packed: Optional[PackedBatch] = None,
+               last_rows=None):
         """Returns (sequence_output [B*S', H] bf16, S') where S' is S padded to a multiple of 64; with
-        ``packed`` the trunk runs on the packed token buffer and returns ([T, H] bf16, None)."""
+        ``packed`` the trunk runs on the packed token buffer and returns ([T, H] bf16, None).
+        Only when the caller passes ``last_rows`` (a LastLayerRows built for this S'; rectangular
+        batches, see ``last_layer_rows_supported``) does the last layer run on those rows alone: the
+        output is then the compact [B*Sq, H] tensor."""
         assert self.flat is not None, "call model.materialize(device) first"
         c, f = self.config, self.flat
         if packed is not None:
@@ -465,7 +630,7 @@ class AlbertPreTrainedModel(nn.Module):
                    f.g(emb + "token_type_embeddings.weight"), f.g(emb + "LayerNorm.weight"),
                    f.g(emb + "LayerNorm.bias")),
             eps=c.layer_norm_eps)
-        return self._layers(x, mask, Sp), Sp
+        return self._layers(x, mask, Sp, last_rows), Sp
 
     def _encode_packed(self, packed: PackedBatch):
         c, f = self.config, self.flat
@@ -485,9 +650,10 @@ class AlbertPreTrainedModel(nn.Module):
             eps=c.layer_norm_eps)
         return self._layers(x, packed, 0)
 
-    def _layers(self, x, mask, Sp):
+    def _layers(self, x, mask, Sp, last_rows=None):
         """Mapping-in GEMM and the shared layer group(s) over a [rows, E] embedding output; ``mask`` is
-        the rectangular (mbias, kvinfo) pair or a PackedBatch."""
+        the rectangular (mbias, kvinfo) pair or a PackedBatch.  With ``last_rows`` (LastLayerRows) the
+        last layer runs on those rows only and the result is [B*Sq, hidden]."""
         c, f = self.config, self.flat
         m = "albert.encoder.embedding_hidden_mapping_in."
         h = ops.linear(x, f.w(m + "weight"), f.w(m + "bias"), f.g(m + "weight"), f.g(m + "bias"))
@@ -501,11 +667,16 @@ class AlbertPreTrainedModel(nn.Module):
             uses = [x for x in range(c.num_hidden_layers) if group_of[x] == g]
             for i in range(c.inner_group_num):
                 lv = views[g][i]
-                if _SHARED_WGRAD and torch.is_grad_enabled():
+                pruned = last_rows is not None and layer == c.num_hidden_layers - 1
+                if last_rows is not None and uses[-1] == c.num_hidden_layers - 1:
+                    # the compact layer accumulates its weight gradients directly, outside the slab
+                    # series: the application before it opens the series
+                    uses = uses[:-1]
+                if not pruned and _SHARED_WGRAD and torch.is_grad_enabled():
                     # backward runs the layers in reverse: the last application is the first to
                     # write the weight's gradient slabs, the first application sums them in
                     lv = dict(lv, wg_first=layer == uses[-1], wg_last=layer == uses[0])
-                h = self._albert_layer(h, lv, mask, Sp)
+                h = self._albert_layer(h, lv, mask, Sp, last_rows if pruned else None)
         return h
 
     def num_parameters(self) -> int:
@@ -534,20 +705,41 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         sd["predictions.decoder.bias"] = sd["predictions.bias"]
         return sd
 
-    def _trunk(self, input_ids, attention_mask, token_type_ids, labels, mlm_positions, pack_sequences, lengths):
-        """Encoder pass of ``forward`` / ``evaluate_batch``: (h, S', PackedBatch or None, row0), row0[b]
-        the row of sequence b's first token in h."""
+    def _trunk(self, input_ids, attention_mask, token_type_ids, labels, mlm_positions, mlm_labels, pack_sequences,
+               lengths):
+        """Encoder pass of ``forward`` / ``evaluate_batch``: (h, S', PackedBatch or None, row0, sel),
+        row0[b] the row of sequence b's first token in h.  With sel (a LastLayerRows) h is the last
+        layer's compact output, S' its slot length."""
         pk = self._packed(pack_sequences, input_ids, attention_mask, token_type_ids, lengths,
                           labels if mlm_positions is None else None)
         if pk is not None:
             h, _ = self.encode(packed=pk)
-            return h, None, pk, pk.row_start  # (b, position) -> row0[b] + position
+            return h, None, pk, pk.row_start, None  # (b, position) -> row0[b] + position
+        sel = self._last_rows(input_ids, labels, mlm_positions, mlm_labels)
+        if sel is not None:
+            # h holds the compact rows: sequence b's [CLS] row at b * Sq, its MLM rows behind it
+            h, _ = self.encode(input_ids, attention_mask, token_type_ids, last_rows=sel)
+            return h, sel.Sq, None, torch.arange(input_ids.shape[0], device=h.device) * sel.Sq, sel
         h, Sp = self.encode(input_ids, attention_mask, token_type_ids)
-        return h, Sp, None, torch.arange(input_ids.shape[0], device=h.device) * Sp
+        return h, Sp, None, torch.arange(input_ids.shape[0], device=h.device) * Sp, None
+
+    def _last_rows(self, input_ids, labels, mlm_positions, mlm_labels):
+        """The compact-row plan of this call's last layer, or None when the full layer runs (no MLM
+        targets, an unsupported head size, the switch off, or nothing to save)."""
+        if not self.last_layer_rows_supported():
+            return None
+        Sp = (input_ids.shape[1] + 63) // 64 * 64
+        if mlm_positions is not None:
+            return LastLayerRows.from_positions(mlm_positions, mlm_labels, Sp)
+        if labels is not None:
+            return LastLayerRows.from_labels(labels, Sp)
+        return None
 
     @staticmethod
-    def _mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels):
+    def _mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels, sel=None):
         """(rows of h under the MLM head, their targets), or (None, None) without MLM targets."""
+        if sel is not None:  # h is the compact output of the last layer
+            return sel.head_rows, sel.targets
         if mlm_positions is None and labels is not None:
             if pk is not None:  # packed labels keep the (b, position) order of the rectangular ones
                 flat_lab = pk.extras["labels"]
@@ -597,9 +789,9 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
                 ids = batch["input_ids"]
                 B, S = ids.shape
                 labels, pos = batch.get("labels"), batch.get("mlm_positions")
-                h, Sp, pk, row0 = self._trunk(ids, batch.get("attention_mask"), batch.get("token_type_ids"), labels,
-                                              pos, None, lengths)
-                rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, pos, batch.get("mlm_labels"))
+                h, Sp, pk, row0, sel = self._trunk(ids, batch.get("attention_mask"), batch.get("token_type_ids"),
+                                                   labels, pos, batch.get("mlm_labels"), None, lengths)
+                rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, pos, batch.get("mlm_labels"), sel)
                 if rows is None:
                     raise ValueError("evaluate_batch needs MLM targets: labels or mlm_positions/mlm_labels")
                 mlm = ops.eval_cross_entropy(self._mlm_logits(h, rows), tgt, topk=(1, 5))
@@ -624,11 +816,11 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         device synchronisation reads them from ``attention_mask``).  Inputs and ``out`` are unchanged.
         """
         B, S = input_ids.shape
-        h, Sp, pk, row0 = self._trunk(input_ids, attention_mask, token_type_ids, labels, mlm_positions,
-                                      pack_sequences, lengths)
+        h, Sp, pk, row0, sel = self._trunk(input_ids, attention_mask, token_type_ids, labels, mlm_positions, mlm_labels,
+                                           pack_sequences, lengths)
         out = {}
         # ---- MLM head on masked positions only
-        rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels)
+        rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels, sel)
         loss = None
         if rows is not None:
             logits = self._mlm_logits(h, rows)

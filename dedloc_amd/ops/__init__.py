@@ -190,6 +190,23 @@ def attn_bwd(qkv, mbias, out, dout, lse, H, S, scale, kvinfo=None, dbias=None):
     return attn_composed_bwd(qkv, mbias, out, dout, lse, H, S, scale, dbias)
 
 
+def attn_fwd_q(q, kv, qcnt, mbias, H, S, scale, kvinfo=None):
+    """Fused attention of compact queries: ``q`` [B*Sq, H*64] holds sequence b's queries in the
+    first ``qcnt[b]`` rows of its slot of ``Sq`` rows (a multiple of 64, at most S); keys and values
+    are all rows of ``kv`` [B*S, 2*H*64] (K | V; a column slice of the fused QKV buffer will do).
+    Returns out [B*Sq, H*64] and lse [B, H, Sq]; slot rows past ``qcnt[b]`` are dead (zeros in out,
+    nothing written to lse).  Each
+    live row equals the same row of ``attn_fwd`` bit for bit.  Head_dim 64 only: there is no
+    head_dim-128, composed or packed form."""
+    return OPS.attn_fwd_q(q, kv, qcnt, mbias, H, S, scale, kvinfo)
+
+
+def attn_bwd_q(q, kv, qcnt, mbias, out, dout, lse, H, S, scale, kvinfo=None, dbias=None):
+    """Backward of ``attn_fwd_q``: (dq [B*Sq, H*64], dkv [B*S, 2*H*64] over all keys, delta
+    [B, H, Sq]); the fused bias gradient in ``dbias`` (fp32 [3*H*64]) counts live rows only."""
+    return OPS.attn_bwd_q(q, kv, qcnt, mbias, out, dout, lse, H, S, scale, kvinfo, dbias)
+
+
 def attn_varlen_fwd(qkv, packed, H, scale):
     """Fused attention over a packed variable-length batch (``data.packing.PackedBatch``): out
     [T, H*D] bf16, lse [H, T] fp32 (log2 units).  Only the head sizes in ``FUSED_HEAD_DIMS``: there

@@ -49,6 +49,10 @@ _SCHEMAS = [
     "attn_fwd(Tensor qkv, Tensor? mbias, int H, int S, float scale, Tensor? kvinfo=None) -> (Tensor, Tensor)",
     "attn_bwd(Tensor qkv, Tensor? mbias, Tensor out, Tensor dout, Tensor lse, int H, int S, float scale, "
     "Tensor? kvinfo=None, Tensor(a!)? dbias=None) -> Tensor",
+    "attn_fwd_q(Tensor q, Tensor kv, Tensor qcnt, Tensor? mbias, int H, int S, float scale, Tensor? kvinfo=None) "
+    "-> (Tensor, Tensor)",
+    "attn_bwd_q(Tensor q, Tensor kv, Tensor qcnt, Tensor? mbias, Tensor out, Tensor dout, Tensor lse, int H, int S, "
+    "float scale, Tensor? kvinfo=None, Tensor(a!)? dbias=None) -> (Tensor, Tensor, Tensor)",
     "attn_varlen_fwd(Tensor qkv, Tensor seqinfo, Tensor seqinfo_host, int H, float scale) -> (Tensor, Tensor)",
     "attn_varlen_bwd(Tensor qkv, Tensor seqinfo, Tensor seqinfo_host, Tensor out, Tensor dout, Tensor lse, int H, "
     "float scale, Tensor(a!)? dbias=None) -> Tensor",
@@ -637,6 +641,61 @@ def _attn_bwd_cpu(qkv, mbias, out, dout, lse, H, S, scale, kvinfo=None, dbias=No
         dbias[:HD] += g[:, :HD].float().sum(0)
         dbias[2 * HD:] += dout.float().reshape(-1, HD).sum(0)
     return g
+
+
+def _compact_q_probs(q, kv, qcnt, mbias, H, S, scale):
+    """fp32 scores of the compact queries against all keys, and which slot rows are live."""
+    T, D = kv.shape[0], kv.shape[1] // (2 * H)
+    B = T // S
+    Sq = q.shape[0] // B
+    if D != 64 or kv.shape[1] != 2 * H * D or q.shape[1] != H * D or Sq % 64 or not 64 <= Sq <= S:
+        raise RuntimeError("dedloc_amd: compact queries need head_dim 64, kv [B*S, 2*H*64] and q [B*Sq, H*64] "
+                           "with Sq a multiple of 64 in 64 .. S")
+    x = kv.float().reshape(B, S, 2, H, D)
+    k, v = x[:, :, 0].transpose(1, 2), x[:, :, 1].transpose(1, 2)
+    qq = q.float().reshape(B, Sq, H, D).transpose(1, 2)
+    s = torch.matmul(qq, k.transpose(-1, -2)) * scale
+    if mbias is not None:
+        s = s + mbias.reshape(B, 1, 1, S) / math.log2(math.e)
+    live = torch.arange(Sq)[None, :] < qcnt.clamp(1, Sq)[:, None].to(torch.long)  # [B, Sq]
+    return qq, k, v, s, live
+
+
+@_impl("attn_fwd_q")
+def _attn_fwd_q_cpu(q, kv, qcnt, mbias, H, S, scale, kvinfo=None):
+    """Attention of compact queries (q [B*Sq, H*D]: sequence b's queries in the first qcnt[b] rows of
+    its slot) over the keys / values of kv [B*S, 2*H*D]: out [B*Sq, H*D], lse [B, H, Sq] (log2
+    units).  Rows past qcnt[b] are dead: zeros in out; their lse is unwritten by the kernels, zero here."""
+    qq, k, v, s, live = _compact_q_probs(q, kv, qcnt, mbias, H, S, scale)
+    B, _, Sq, D = qq.shape
+    lse = torch.logsumexp(s, -1) * math.log2(math.e)
+    o = torch.matmul(torch.softmax(s, -1), v).transpose(1, 2).reshape(B * Sq, H * D)
+    o = torch.where(live.reshape(-1, 1), o, torch.zeros_like(o))
+    return _bf(o), torch.where(live[:, None, :], lse, torch.zeros_like(lse)).contiguous()
+
+
+@_impl("attn_bwd_q")
+def _attn_bwd_q_cpu(q, kv, qcnt, mbias, out, dout, lse, H, S, scale, kvinfo=None, dbias=None):
+    """Backward of ``attn_fwd_q``: (dq [B*Sq, H*D], dkv [B*S, 2*H*D] = dK | dV over all keys, delta
+    [B, H, Sq]); dead rows give nothing to dkv or to the bias gradient."""
+    qq, k, v, s, live = _compact_q_probs(q, kv, qcnt, mbias, H, S, scale)
+    B, _, Sq, D = qq.shape
+    lv = live[:, None, :, None].float()
+    p = torch.softmax(s, -1) * lv
+    do = dout.float().reshape(B, Sq, H, D).transpose(1, 2) * lv
+    o = out.float().reshape(B, Sq, H, D).transpose(1, 2) * lv
+    dv = torch.matmul(p.transpose(-1, -2), do)
+    dp = torch.matmul(do, v.transpose(-1, -2))
+    delta = (do * o).sum(-1, keepdim=True)
+    ds = p * (dp - delta)
+    dq = _bf((torch.matmul(ds, k) * scale).transpose(1, 2).reshape(B * Sq, H * D))
+    dk = torch.matmul(ds.transpose(-1, -2), qq) * scale
+    dkv = _bf(torch.stack([dk, dv], dim=2).permute(0, 3, 2, 1, 4).reshape(B * S, 2 * H * D))  # B,H,2,S,D
+    if dbias is not None:  # query: colsum(dQ); key: 0; value: colsum(dout), live rows only
+        HD = H * D
+        dbias[:HD] += dq.float().sum(0)
+        dbias[2 * HD:] += do.transpose(1, 2).reshape(-1, HD).sum(0)
+    return dq, dkv, delta.squeeze(-1).contiguous()
 
 
 def packed_layout(seqinfo_host, T):
