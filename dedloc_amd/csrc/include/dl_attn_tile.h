@@ -86,7 +86,7 @@ __device__ __forceinline__ void dma4(const void* g, uint32_t lds) {
   asm volatile("s_mov_b32 m0, %0\n\tglobal_load_lds_dword %1, off" ::"s"(lds), "v"(g) : "memory", "m0");
 }
 
-// Prologue order in the RING kernels: issue the first NBUF-1 stages, THEN the block's compiler-visible
+// Prologue order in the ring kernels: issue the first NBUF-1 stages, THEN the block's compiler-visible
 // register loads (Q / dO / K / V rows, lse ...), then this real s_waitcnt vmcnt(0) (the builtin, so
 // the compiler's wait-count pass sees it): the asm DMAs are invisible to that pass, and a
 // compiler-placed partial vmcnt for those register loads inside the tile loop would drain the ring.
@@ -133,19 +133,15 @@ __device__ __forceinline__ void wait_stages(int ahead, bool bias) {
   else wait_cnt<PIECES>(ahead);
 }
 
-// store 4 consecutive bf16 (8 bytes)
-__device__ __forceinline__ void store4(bf16_t* p, float a, float b, float c, float d) {
-  uint2 v;
-  v.x = (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
-  v.y = (uint32_t)f2bf(c) | ((uint32_t)f2bf(d) << 16);
-  *reinterpret_cast<uint2*>(p) = v;
-}
-
+// 4 floats -> 4 consecutive bf16 (8 bytes)
 __device__ __forceinline__ uint2 pack4(float a, float b, float c, float d) {
   uint2 v;
   v.x = (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16);
   v.y = (uint32_t)f2bf(c) | ((uint32_t)f2bf(d) << 16);
   return v;
+}
+__device__ __forceinline__ void store4(bf16_t* p, float a, float b, float c, float d) {
+  *reinterpret_cast<uint2*>(p) = pack4(a, b, c, d);
 }
 
 // Wide store of one 64-column bf16 row held as two 32x32 accumulator tiles (cdna_hip_programming.md

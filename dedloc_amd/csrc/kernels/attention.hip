@@ -28,34 +28,33 @@ namespace {
 
 constexpr int HD = 64;          // head dim
 
-// cooperative 64-row x 64-col tile stage: 256 threads, 2 x 16 B each (two named registers —
-// an indexed array of uint4 was demoted to scratch by hipcc)
-struct TileRegs { uint4 a, b; };
+// The one launched configuration.  Blocks are 4 waves (256 threads, two blocks per CU); a wave of
+// the forward and dQ kernels carries QS = 2 query sub-blocks of 32 rows, a wave of the dK/dV kernel
+// one 32-key sub-block; every kernel stages its tiles through the LDS-DMA ring below.  With QS = 2
+// every K fragment (row reads) and V fragment (tr-reads) read from LDS feeds two MFMAs, and each
+// wave carries two independent softmax chains the scheduler can interleave (the loops are
+// latency-bound: PMC, profiles/README.md "Round 2: attention latency work").  The forms measured
+// against it and no longer in the file:
+//   - one sub-block per wave (forward, dQ): forward 555 us against 507 us, dQ backward 5.5% slower
+//     (same section; profiles/attn_bwd_dq_qs_ab_b256.jsonl);
+//   - 8-wave forward blocks (one 512-query block per head at S = 512, K / V staged once per head):
+//     5% slower (profiles/attn_fwd_nw8_ab_b256.jsonl);
+//   - two key sub-blocks per wave in dK/dV: its 128 accumulator registers need the whole register
+//     file, so it ran one wave per SIMD (launch bound 256 x 1) and measured 8% slower
+//     (profiles/attn_dkdv_ks_ab_b256.jsonl);
+//   - register staging (global -> VGPR -> ds_write, two-deep) instead of the ring: 26-43% of wave
+//     cycles parked in s_waitcnt / barrier (profiles/attn_pmc_regstaged_b256.txt), the forward's
+//     second sub-block spilled (the ring frees 16 staging VGPRs), and dK/dV was 3.5% slower at
+//     B = 512 (profiles/README.md, "dK/dV through the LDS-DMA ring").
+constexpr int QS = 2;
 
-__device__ __forceinline__ uint4 tile_ld1(const bf16_t* g, long ld, int row0, int rows_valid, int idx) {
-  const int row = min(row0 + (idx >> 3), rows_valid - 1);
-  return *reinterpret_cast<const uint4*>(g + (long)row * ld + (idx & 7) * 8);
-}
-
-__device__ __forceinline__ void tile_load(TileRegs& t, const bf16_t* g, long ld, int row0, int rows_valid) {
-  t.a = tile_ld1(g, ld, row0, rows_valid, threadIdx.x);
-  t.b = tile_ld1(g, ld, row0, rows_valid, threadIdx.x + 256);
-}
-
-__device__ __forceinline__ void tile_store(const TileRegs& t, uint8_t* tile) {
-  const int i0 = threadIdx.x, i1 = threadIdx.x + 256;
-  *reinterpret_cast<uint4*>(tile + chunk_off(i0 >> 3, i0 & 7)) = t.a;
-  *reinterpret_cast<uint4*>(tile + chunk_off(i1 >> 3, i1 & 7)) = t.b;
-}
-
-// ---- LDS-DMA staging ring (RING kernels) ---------------------------------------------------------
+// ---- LDS-DMA staging ring ------------------------------------------------------------------------
 // Each pipeline stage holds the two 64x64 tiles of one key (or query) block plus 64-128 floats of
 // per-row data, written by global_load_lds (no VGPR round trip, no ds_write).  NBUF stages: the
 // loads of stage s + NBUF - 1 are issued while stage s computes, and a counted vmcnt waits for
-// stage s only (PMC on the register-staged form: 26-43% of wave cycles parked in s_waitcnt /
-// barrier, scripts/gpu_r2_pmc.sh).  LDS-DMA writes lane-linearly (lane i -> base + 16 i), so the
-// XOR swizzle of chunk_off is applied to the SOURCE: lane i of 1-KiB piece p loads row 8p + i/8,
-// chunk (i & 7) ^ swz(row).  The DMA primitives and the counted waits are in dl_attn_tile.h.
+// stage s only.  LDS-DMA writes lane-linearly (lane i -> base + 16 i), so the XOR swizzle of
+// chunk_off is applied to the SOURCE: lane i of 1-KiB piece p loads row 8p + i/8, chunk
+// (i & 7) ^ swz(row).  The DMA primitives and the counted waits are in dl_attn_tile.h.
 // Two stages: the next tile's DMA is issued at the top of the current tile and has a whole tile of
 // MFMA / softmax work to land (4 stages measured 1.3% slower forward, 0.5% slower dQ at B=512:
 // profiles/r5_attn_ring_depth_occupancy.jsonl).
@@ -74,68 +73,41 @@ constexpr int STAGE = 2 * TILE_BYTES + 512;
 // RESCALE_THR, the XCD-aware block order (block_id), kv_end_of and the cross-half reductions are in
 // dl_attn_tile.h.
 
-// Forward tile loop over key tiles [kt0, kt1) of nt, with the next tile's K/V (and per-key bias)
-// prefetched through registers while this tile computes (T14).  Tile kt0 must already be staged.
-// LEAN: unmasked tiles — raw scores, the softmax scale rides in the exp FMA, no bias reads.
-// !LEAN: s = s*sl2 + bias[key] with the bias staged in LDS (additive mask or 0/-1e30 from the
-// key length).  The two instantiations run as consecutive loops (lean body, then the boundary
-// tile), never in one loop body, so they do not add register pressure to each other.
-struct FwdCtx {
+// The K / V ring of the forward and dQ kernels: stage s is key tile s (K, V and, under a generic
+// additive mask, its 64 bias floats mb_g[64 s ..]) in slot s % NBUF of smem.
+struct KvRing {
   const bf16_t* Kg;
   const bf16_t* Vg;
   long ld;
-  int S, kv_end;
   const float* mb_g;
-  float sl2;
   uint8_t* smem;
-  float* mbs;
   int w, lane;
-  // RING: issue stage s (key tile s) into ring slot s % NBUF (NW waves share the tile pieces)
-  template <int NW = 4>
   __device__ __forceinline__ void issue(int s) const {
     uint8_t* slot = smem + (s % NBUF) * STAGE;
-    dma_tile<NW>(Kg, ld, s * 64, slot, w, lane);
-    dma_tile<NW>(Vg, ld, s * 64, slot + TILE_BYTES, w, lane);
+    dma_tile(Kg, ld, s * 64, slot, w, lane);
+    dma_tile(Vg, ld, s * 64, slot + TILE_BYTES, w, lane);
     if (mb_g) dma_f32x64(mb_g + s * 64, slot + 2 * TILE_BYTES, lane);
   }
 };
 
-__device__ __forceinline__ float key_bias(const FwdCtx& c, int key) {
-  return c.mb_g ? c.mb_g[key] : (key < c.kv_end ? 0.f : NEG_BIG);
-}
-
-// QS = 32-row query sub-blocks per wave (1 or 2).  With QS = 2 every K fragment (row reads) and V
-// fragment (tr-reads) read from LDS feeds two MFMAs, and each wave carries two independent softmax
-// chains the scheduler can interleave (the loop is latency-bound: PMC, profiles/README.md).
-template <bool LEAN, bool RING, int QS, int NW>
-__device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int nt, const bf16x8 (&qf)[QS][4],
-                                          floatx16 (&o)[QS][2], float (&m)[QS], float (&l)[QS], int r, int hh,
-                                          int lane) {
-  TileRegs kr, vr;
-  float mbr = 0.f;
+// Forward tile loop over key tiles [kt0, kt1) of nt; the ring's prologue has issued tile 0 (the
+// first NBUF - 1 stages).
+// LEAN: unmasked tiles — raw scores, the softmax scale rides in the exp FMA, no bias reads.
+// !LEAN: s = s*sl2 + bias[key] with the bias staged in LDS (additive mask or 0/-1e30 from the
+// key length).  The two instantiations run as consecutive loops (lean body, then the boundary
+// tile), never in one loop body, so they do not add register pressure to each other.
+template <bool LEAN>
+__device__ __forceinline__ void fwd_tiles(const KvRing& c, int kv_end, float sl2, int kt0, int kt1, int nt,
+                                          const bf16x8 (&qf)[QS][4], floatx16 (&o)[QS][2], float (&m)[QS],
+                                          float (&l)[QS], int r, int hh, int lane) {
   for (int kt = kt0; kt < kt1; ++kt) {
-    const uint8_t* Ks;
-    const float* mb;
-    bool more = false;
-    if constexpr (RING) {
-      // stage kt landed (this wave) -> barrier: every wave's pieces landed and every wave is done
-      // with slot (kt - 1) % NBUF, which the stage issued next overwrites
-      wait_stages<16 / NW>(min(nt - 1 - kt, NBUF - 2), c.mb_g != nullptr);
-      __syncthreads();
-      if (kt + NBUF - 1 < nt) c.template issue<NW>(kt + NBUF - 1);
-      Ks = c.smem + (kt % NBUF) * STAGE;
-      mb = reinterpret_cast<const float*>(Ks + 2 * TILE_BYTES);
-    } else {
-      const int cur = kt & 1;
-      Ks = c.smem + cur * 2 * TILE_BYTES;
-      mb = c.mbs + cur * 64;
-      more = kt + 1 < nt;
-      if (more) {  // issue next tile's loads early; they land under the MFMAs below
-        tile_load(kr, c.Kg, c.ld, (kt + 1) * 64, c.S);
-        tile_load(vr, c.Vg, c.ld, (kt + 1) * 64, c.S);
-        if (threadIdx.x < 64) mbr = key_bias(c, (kt + 1) * 64 + threadIdx.x);
-      }
-    }
+    // stage kt landed (this wave) -> barrier: every wave's pieces landed and every wave is done
+    // with slot (kt - 1) % NBUF, which the stage issued next overwrites
+    wait_stages(min(nt - 1 - kt, NBUF - 2), c.mb_g != nullptr);
+    __syncthreads();
+    if (kt + NBUF - 1 < nt) c.issue(kt + NBUF - 1);
+    const uint8_t* Ks = c.smem + (kt % NBUF) * STAGE;
+    const float* mb = reinterpret_cast<const float*>(Ks + 2 * TILE_BYTES);
     const uint8_t* Vs = Ks + TILE_BYTES;
     floatx16 s[QS][2];
 #pragma unroll
@@ -155,17 +127,17 @@ __device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int
 #pragma unroll
     for (int u = 0; u < QS; ++u) {
       if (!LEAN) {
-        if (!RING || c.mb_g) {
+        if (c.mb_g) {
 #pragma unroll
           for (int j = 0; j < 2; ++j)
 #pragma unroll
-            for (int i = 0; i < 16; ++i) s[u][j][i] = fmaf(s[u][j][i], c.sl2, mb[32 * j + crow(i, hh)]);
-        } else {  // RING stages carry the generic additive bias only; the length mask is computed here
+            for (int i = 0; i < 16; ++i) s[u][j][i] = fmaf(s[u][j][i], sl2, mb[32 * j + crow(i, hh)]);
+        } else {  // stages carry the generic additive bias only; the length mask is computed here
 #pragma unroll
           for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int i = 0; i < 16; ++i)
-              s[u][j][i] = fmaf(s[u][j][i], c.sl2, kt * 64 + 32 * j + crow(i, hh) < c.kv_end ? 0.f : NEG_BIG);
+              s[u][j][i] = fmaf(s[u][j][i], sl2, kt * 64 + 32 * j + crow(i, hh) < kv_end ? 0.f : NEG_BIG);
         }
       }
       // row max as four independent max3 chains of 8 scores (depth 6 instead of 16), then the halves
@@ -182,7 +154,7 @@ __device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int
       float mx = vmax3(vmax3(mc[0], mc[1], s[u][0][7]), vmax3(mc[2], mc[3], s[u][0][15]),
                        vmax3(s[u][1][7], s[u][1][15], mc[0]));
       mx = half_max(mx);
-      if (LEAN) mx *= c.sl2;
+      if (LEAN) mx *= sl2;
       const bool grow = mx > m[u] + RESCALE_THR;
       if (__ballot(grow) != 0) {  // rare after the first tile: rescale O and l to the new max
         const float mn = grow ? mx : m[u];
@@ -200,7 +172,7 @@ __device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int
       for (int j = 0; j < 2; ++j)
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const float pv = __builtin_amdgcn_exp2f(LEAN ? fmaf(s[u][j][i], c.sl2, nm) : s[u][j][i] + nm);
+          const float pv = __builtin_amdgcn_exp2f(LEAN ? fmaf(s[u][j][i], sl2, nm) : s[u][j][i] + nm);
           s[u][j][i] = pv;
           rsa[i & 7] += pv;
         }
@@ -221,15 +193,6 @@ __device__ __forceinline__ void fwd_tiles(const FwdCtx& c, int kt0, int kt1, int
           for (int u = 0; u < QS; ++u) o[u][t] = mfma32(vfr, pb[u], o[u][t]);
         }
       }
-    if constexpr (!RING) {
-      if (more) {
-        uint8_t* Kn = c.smem + ((kt & 1) ^ 1) * 2 * TILE_BYTES;
-        tile_store(kr, Kn);
-        tile_store(vr, Kn + TILE_BYTES);
-        if (threadIdx.x < 64) c.mbs[((kt & 1) ^ 1) * 64 + threadIdx.x] = mbr;
-      }
-      __syncthreads();
-    }
   }
 }
 
@@ -262,17 +225,11 @@ __device__ __forceinline__ long q_stat(const CompactArg<CQ>& cq, int b, int h, i
   if constexpr (CQ) return ((long)b * H + h) * cq.Sq;
   else return seq_stat<VARLEN>(b, h, H, S, T, rb);
 }
-// first row of sequence b's queries / outputs, the rows its query tiles may address, and head h's
-// first query element
+// first row of sequence b's queries / outputs, and head h's first query element
 template <bool CQ>
 __device__ __forceinline__ long q_first(const CompactArg<CQ>& cq, int b, long rb) {
   if constexpr (CQ) return (long)b * cq.Sq;
   else return rb;
-}
-template <bool CQ>
-__device__ __forceinline__ int q_slot(const CompactArg<CQ>& cq, int S) {
-  if constexpr (CQ) return cq.Sq;
-  else return S;
 }
 template <bool CQ>
 __device__ __forceinline__ const bf16_t* q_head(const CompactArg<CQ>& cq, const bf16_t* qkv, long ld, long ldo, long rb,
@@ -295,29 +252,27 @@ __device__ __forceinline__ int q_rows(const CompactArg<CQ>& cq, int b, int S) {
   else return S;
 }
 
-// Block = NW waves x QS x 32 query rows of one (batch, head).  NW = 8 (ring only): one 512-query
-// block per head at S = 512, so K / V are staged once per head, and each SIMD's two waves belong
-// to one block.
+// Block = 4 waves x QS x 32 query rows of one (batch, head).
 // VARLEN: the packed layout (seq_rows .. seq_stat in dl_attn_tile.h): kvinfo is seqinfo, S_ is T, the grid's x
 // extent covers the largest slot and a block past its own slot leaves before any DMA or barrier.
-template <bool RING, int QS, int NW = 4, bool VARLEN = false, typename... CQA>
-__global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, long ld,
+template <bool VARLEN, typename... CQA>
+__global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                           const float* __restrict__ mbias,
                                                           const int* __restrict__ kvinfo, bf16_t* __restrict__ out,
                                                           long ldo, float* __restrict__ lse, int B, int H, int S_,
                                                           float sl2, int xcd, CQA... cqa) {
   constexpr bool CQ = sizeof...(CQA) == 1;
   const CompactArg<CQ> cq = compact_arg(cqa...);
-  __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 2 * 64 * 4];
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * STAGE];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int S = seq_rows<VARLEN>(kvinfo, b, S_);
   const int nq = q_rows<CQ>(cq, b, S);
   if constexpr (VARLEN || CQ) {
-    if (bid.x * (32 * QS * NW) >= nq) {  // uniform over the block
+    if (bid.x * (128 * QS) >= nq) {  // uniform over the block
       if constexpr (CQ) {  // a block of dead rows: zeros
-        const int q0 = bid.x * (32 * QS * NW);
+        const int q0 = bid.x * (128 * QS);
         zero_rows64(out + ((long)b * cq.Sq + q0) * ldo + h * HD, ldo, cq.Sq - q0);
       }
       return;
@@ -327,37 +282,23 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
   const long qb = q_first<CQ>(cq, b, rb);
   const long ldq = CQ ? ldo : ld;
   const bf16_t* Qg = q_head<CQ>(cq, qkv, ld, ldo, rb, qb, h);
+  const bf16_t* Kg = qkv + rb * ld + (CQ ? 0L : (long)H * HD) + h * HD;
+  const bf16_t* Vg = qkv + rb * ld + (CQ ? (long)H * HD : 2L * H * HD) + h * HD;
   bool use_len;
-  FwdCtx c;
-  c.Kg = qkv + rb * ld + (CQ ? 0L : (long)H * HD) + h * HD;
-  c.Vg = qkv + rb * ld + (CQ ? (long)H * HD : 2L * H * HD) + h * HD;
-  c.ld = ld;
-  c.S = S;
-  c.kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
-  c.mb_g = (!use_len && mbias) ? mbias + rb : nullptr;
-  c.sl2 = sl2;
-  c.smem = smem;
-  c.mbs = reinterpret_cast<float*>(smem + 4 * TILE_BYTES);
-  c.w = w;
-  c.lane = lane;
-
-  static_assert(NW == 4 || (NW == 8 && RING), "8-wave blocks stage through the ring");
-  const int nt = (c.kv_end + 63) / 64;
-  if constexpr (RING) {
-    for (int s0 = 0; s0 < NBUF - 1 && s0 < nt; ++s0) c.template issue<NW>(s0);
-  }
+  const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
+  const int nt = (kv_end + 63) / 64;
+  const KvRing ring{Kg, Vg, ld, (!use_len && mbias) ? mbias + rb : nullptr, smem, w, lane};
+  for (int s0 = 0; s0 < NBUF - 1 && s0 < nt; ++s0) ring.issue(s0);
   int q[QS];
   bf16x8 qf[QS][4];
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
-    q[u] = bid.x * (32 * QS * NW) + w * (32 * QS) + 32 * u + r;
+    q[u] = bid.x * (128 * QS) + w * (32 * QS) + 32 * u + r;
     const int qc = min(q[u], nq - 1);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) qf[u][ks] = gload8(Qg + (long)qc * ldq + ks * 16 + 8 * hh);
-    if constexpr (RING) {
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) settle(qf[u][ks]);
-    }
+    for (int ks = 0; ks < 4; ++ks) settle(qf[u][ks]);
   }
 
   floatx16 o[QS][2];
@@ -372,23 +313,12 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
       for (int i = 0; i < 16; ++i) o[u][t][i] = 0.f;
   }
 
-  if constexpr (RING) {
-    wait_vm_all();
-  } else {
-    TileRegs kr, vr;
-    tile_load(kr, c.Kg, ld, 0, S);
-    tile_load(vr, c.Vg, ld, 0, S);
-    const float mbr = threadIdx.x < 64 ? key_bias(c, threadIdx.x) : 0.f;
-    tile_store(kr, smem);
-    tile_store(vr, smem + TILE_BYTES);
-    if (threadIdx.x < 64) c.mbs[threadIdx.x] = mbr;
-    __syncthreads();
-  }
+  wait_vm_all();
   // lean tiles first (every tile when there is no mask), then the masked remainder: the boundary
   // tile of a length mask, or all tiles of a generic additive mask
-  const int nlean = c.mb_g ? 0 : c.kv_end / 64;
-  fwd_tiles<true, RING, QS, NW>(c, 0, nlean, nt, qf, o, m, l, r, hh, lane);
-  fwd_tiles<false, RING, QS, NW>(c, nlean, nt, nt, qf, o, m, l, r, hh, lane);
+  const int nlean = ring.mb_g ? 0 : kv_end / 64;
+  fwd_tiles<true>(ring, kv_end, sl2, 0, nlean, nt, qf, o, m, l, r, hh, lane);
+  fwd_tiles<false>(ring, kv_end, sl2, nlean, nt, nt, qf, o, m, l, r, hh, lane);
 
 #pragma unroll
   for (int u = 0; u < QS; ++u) {
@@ -403,9 +333,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 1 : 2) void attn_fwd_kernel(cons
 
 // ------------------------------------------------------------------------------------------ bwd dq
 // Also computes delta = rowsum(dO * O) for its queries and publishes it for the dkdv kernel.
-// QS = 32-row query sub-blocks per wave (as in the forward: every K / V fragment read from LDS
-// feeds QS MFMAs, and each wave carries QS independent chains).
-template <bool RING, int QS, bool VARLEN = false, typename... CQA>
+template <bool VARLEN, typename... CQA>
 __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __restrict__ qkv, long ld,
                                                              const float* __restrict__ mbias,
                                                              const int* __restrict__ kvinfo,
@@ -416,8 +344,8 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
                                                              float scale, int xcd, CQA... cqa) {
   constexpr bool CQ = sizeof...(CQA) == 1;
   const CompactArg<CQ> cq = compact_arg(cqa...);
-  // tail: mask bias (the epilogue reuses the first 2 KiB for the waves' bias-gradient partials)
-  __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 4 * 64 * 4];
+  // (the epilogue reuses the first 2 KiB for the waves' bias-gradient partials)
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * STAGE];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
@@ -441,17 +369,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
   bool use_len;
   const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
   const float* mb_g = (!use_len && mbias) ? mbias + rb : nullptr;
-  float* mbs = reinterpret_cast<float*>(smem + 4 * TILE_BYTES);
   const int nt = (kv_end + 63) / 64;
-  auto issue = [&](int st) {  // RING: key tile st -> slot st % NBUF
-    uint8_t* slot = smem + (st % NBUF) * STAGE;
-    dma_tile(Kg, ld, st * 64, slot, w, lane);
-    dma_tile(Vg, ld, st * 64, slot + TILE_BYTES, w, lane);
-    if (mb_g) dma_f32x64(mb_g + st * 64, slot + 2 * TILE_BYTES, lane);
-  };
-  if constexpr (RING) {
-    for (int s0 = 0; s0 < NBUF - 1 && s0 < nt; ++s0) issue(s0);
-  }
+  const KvRing ring{Kg, Vg, ld, mb_g, smem, w, lane};
+  for (int s0 = 0; s0 < NBUF - 1 && s0 < nt; ++s0) ring.issue(s0);
 
   int q[QS];
   bf16x8 qf[QS][4], df[QS][4];
@@ -472,14 +392,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
     }
     dl[u] += __shfl_xor(dl[u], 32, 64);
     l2[u] = lse[q_stat<VARLEN, CQ>(cq, b, h, H, S, S_, rb) + qc];
-    if constexpr (RING) {
-      settle(l2[u]);
-      settle(dl[u]);
+    settle(l2[u]);
+    settle(dl[u]);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        settle(qf[u][ks]);
-        settle(df[u][ks]);
-      }
+    for (int ks = 0; ks < 4; ++ks) {
+      settle(qf[u][ks]);
+      settle(df[u][ks]);
     }
   }
   // (delta is stored after the tile loop: a store issued here would sit in the vmcnt queue ahead of
@@ -493,19 +411,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
 #pragma unroll
       for (int i = 0; i < 16; ++i) dq[u][t][i] = 0.f;
 
-  TileRegs kr, vr;
-  float mbr = 0.f;
-  if constexpr (RING) {
-    wait_vm_all();
-  } else {
-    tile_load(kr, Kg, ld, 0, S);
-    tile_load(vr, Vg, ld, 0, S);
-    if (threadIdx.x < 64) mbr = mb_g ? mb_g[threadIdx.x] : 0.f;
-    tile_store(kr, smem);
-    tile_store(vr, smem + TILE_BYTES);
-    if (threadIdx.x < 64) mbs[threadIdx.x] = mbr;
-    __syncthreads();
-  }
+  wait_vm_all();
 
   // One tile body, two instantiations run as consecutive loops (as in the forward), so the masked
   // form adds no register pressure or branches to the lean one: LEAN for the unmasked tiles
@@ -520,23 +426,11 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
   if constexpr (!LEAN) settle(tm);
   const int lm = tm & 63, rm = tm & 31, hm = (tm >> 5) & 1;
   for (int kt = kt0; kt < kt1; ++kt) {
-    const uint8_t* Ks;
-    const float* mb;
-    if constexpr (RING) {
-      wait_stages(min(nt - 1 - kt, NBUF - 2), mb_g != nullptr);
-      __syncthreads();
-      if (kt + NBUF - 1 < nt) issue(kt + NBUF - 1);
-      Ks = smem + (kt % NBUF) * STAGE;
-      mb = reinterpret_cast<const float*>(Ks + 2 * TILE_BYTES);
-    } else {
-      Ks = smem + (kt & 1) * 2 * TILE_BYTES;
-      mb = mbs + (kt & 1) * 64;
-      if (kt + 1 < nt) {
-        tile_load(kr, Kg, ld, (kt + 1) * 64, S);
-        tile_load(vr, Vg, ld, (kt + 1) * 64, S);
-        if (threadIdx.x < 64) mbr = mb_g ? mb_g[(kt + 1) * 64 + threadIdx.x] : 0.f;
-      }
-    }
+    wait_stages(min(nt - 1 - kt, NBUF - 2), mb_g != nullptr);
+    __syncthreads();
+    if (kt + NBUF - 1 < nt) ring.issue(kt + NBUF - 1);
+    const uint8_t* Ks = smem + (kt % NBUF) * STAGE;
+    const float* mb = reinterpret_cast<const float*>(Ks + 2 * TILE_BYTES);
     const uint8_t* Vs = Ks + TILE_BYTES;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -591,21 +485,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
         }
       }
     }
-    if constexpr (!RING) {
-      if (kt + 1 < nt) {
-        uint8_t* Kn = smem + ((kt & 1) ^ 1) * 2 * TILE_BYTES;
-        tile_store(kr, Kn);
-        tile_store(vr, Kn + TILE_BYTES);
-        if (threadIdx.x < 64) mbs[((kt & 1) ^ 1) * 64 + threadIdx.x] = mbr;
-      }
-      __syncthreads();
-    }
   }
   };
   const int nlean = mb_g ? 0 : kv_end / 64;
   tiles(std::true_type{}, 0, nlean);
   tiles(std::false_type{}, nlean, nt);
-  if constexpr (RING) __syncthreads();  // every wave is done with the ring before the epilogue reuses it
+  __syncthreads();  // every wave is done with the ring before the epilogue reuses it
   // The epilogue forms its lane coordinates again from the thread index, behind an opaque copy, so
   // that none of them stays live across the tile loops (the loops run at the 256-register limit).
   int tid = threadIdx.x;
@@ -679,23 +564,21 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
 }
 
 // ------------------------------------------------------------------------------------------ bwd dkdv
-// KS = 32-key sub-blocks per wave: with KS = 2 every Q / dO fragment read from LDS feeds two
-// MFMAs; the dK/dV accumulators (128 registers) need the whole 512-entry register file, so that
-// form runs one wave per SIMD (launch bound 256 x 1) and hides latency by ILP instead of waves.
-template <bool RING, int KS, bool VARLEN = false, typename... CQA>
-__global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
+// Block = 4 waves x 32 keys of one (batch, head); the ring stages the query tiles (Q, dO, lse, delta).
+template <bool VARLEN, typename... CQA>
+__global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(
     const bf16_t* __restrict__ qkv, long ld, const float* __restrict__ mbias, const int* __restrict__ kvinfo,
     const bf16_t* __restrict__ dout, long ldo, const float* __restrict__ lse, const float* __restrict__ delta,
     bf16_t* __restrict__ dqkv, int B, int H, int S_, float sl2, float scale, int xcd, CQA... cqa) {
   constexpr bool CQ = sizeof...(CQA) == 1;
   const CompactArg<CQ> cq = compact_arg(cqa...);
-  __shared__ __attribute__((aligned(16))) uint8_t smem[RING ? NBUF * STAGE : 4 * TILE_BYTES + 2 * 2 * 64 * 4];
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * STAGE];
   const BlockId bid = block_id(xcd);
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int S = seq_rows<VARLEN>(kvinfo, b, S_);
   if constexpr (VARLEN) {
-    if (bid.x * (128 * KS) >= S) return;  // uniform over the block
+    if (bid.x * 128 >= S) return;  // uniform over the block
   }
   const long rb = seq_base<VARLEN>(kvinfo, b, S);
   const int nq = q_rows<CQ>(cq, b, S);
@@ -717,16 +600,20 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
     dkv_g = dqkv;
     ldd = ld;
   }
-  float* rowv = reinterpret_cast<float*>(smem + 4 * TILE_BYTES);  // [2 buf][lse 64 | delta 64]
 
-  int k[KS];
+  // This lane's key row.  It stays a one-element array, filled and read in one-trip `u` loops
+  // where it forms addresses (here, the all-padding exit, the K / V row loads), and the score
+  // MFMA pair of the tile loop keeps such a loop too: those are the places where the plain scalar
+  // form compiles to other code (another association of the row's address sums, swapped operands
+  // of one v_pk_mul_f32), and this kernel's code is held byte-identical across source clean-ups.
+  int k[1];
 #pragma unroll
-  for (int u = 0; u < KS; ++u) k[u] = bid.x * (128 * KS) + w * (32 * KS) + 32 * u + r;
+  for (int u = 0; u < 1; ++u) k[u] = bid.x * 128 + w * 32 + 32 * u + r;
   bool use_len;
   const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
-  if (use_len && bid.x * (128 * KS) >= kv_end) {  // every key of this block is padding: dK = dV = 0
+  if (use_len && bid.x * 128 >= kv_end) {  // every key of this block is padding: dK = dV = 0
 #pragma unroll
-    for (int u = 0; u < KS; ++u) {
+    for (int u = 0; u < 1; ++u) {
       if (k[u] < S) {
         bf16_t* dkp = dkv_g + (rb + k[u]) * ldd + (long)H * HD + h * HD;
         bf16_t* dvp = dkv_g + (rb + k[u]) * ldd + 2L * H * HD + h * HD;
@@ -741,57 +628,39 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
   }
   // query tiles: all of the sequence's, or (CQ) the slot's tiles that hold a live row
   const int nt = CQ ? (nq + 63) / 64 : S / 64;
-  auto issue = [&](int st) {  // RING: query tile st -> slot st % NBUF; waves 0-1 fetch lse, 2-3 delta
+  auto issue = [&](int st) {  // query tile st -> slot st % NBUF; waves 0-1 fetch lse, 2-3 delta
     uint8_t* slot = smem + (st % NBUF) * STAGE;
     dma_tile(Qg, ldq, st * 64, slot, w, lane);
     dma_tile(dOg, ldo, st * 64, slot + TILE_BYTES, w, lane);
     dma_f32x64((w < 2 ? lse_g : del_g) + st * 64, slot + 2 * TILE_BYTES + (w < 2 ? 0 : 256), lane);
   };
-  if constexpr (RING) {
-    for (int s0 = 0; s0 < NBUF - 1 && s0 < nt; ++s0) issue(s0);
-  }
-  bf16x8 kf[KS][4], vf[KS][4];
-  float mbk[KS];
+  for (int s0 = 0; s0 < NBUF - 1 && s0 < nt; ++s0) issue(s0);
+  bf16x8 kf[4], vf[4];
+  float mbk;
 #pragma unroll
-  for (int u = 0; u < KS; ++u) {
+  for (int u = 0; u < 1; ++u) {
     const int kc = min(k[u], S - 1);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
-      kf[u][ks] = gload8(Kg + (long)kc * ld + ks * 16 + 8 * hh);
-      vf[u][ks] = gload8(Vg + (long)kc * ld + ks * 16 + 8 * hh);
+      kf[ks] = gload8(Kg + (long)kc * ld + ks * 16 + 8 * hh);
+      vf[ks] = gload8(Vg + (long)kc * ld + ks * 16 + 8 * hh);
     }
-    mbk[u] = use_len ? (k[u] < kv_end ? 0.f : NEG_BIG) : (mbias ? mbias[rb + kc] : 0.f);
-    if constexpr (RING) {
-      settle(mbk[u]);
+    mbk = use_len ? (k[u] < kv_end ? 0.f : NEG_BIG) : (mbias ? mbias[rb + kc] : 0.f);
+    settle(mbk);
 #pragma unroll
-      for (int ks = 0; ks < 4; ++ks) {
-        settle(kf[u][ks]);
-        settle(vf[u][ks]);
-      }
+    for (int ks = 0; ks < 4; ++ks) {
+      settle(kf[ks]);
+      settle(vf[ks]);
     }
   }
 
-  floatx16 dk[KS][2], dv[KS][2];
+  floatx16 dk[2], dv[2];
 #pragma unroll
-  for (int u = 0; u < KS; ++u)
+  for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) { dk[u][t][i] = 0.f; dv[u][t][i] = 0.f; }
+    for (int i = 0; i < 16; ++i) { dk[t][i] = 0.f; dv[t][i] = 0.f; }
 
-  TileRegs qr, dr;
-  float rv = 0.f;
-  if constexpr (RING) {
-    wait_vm_all();
-  } else {
-    tile_load(qr, Qg, ldq, 0, q_slot<CQ>(cq, S));
-    tile_load(dr, dOg, ldo, 0, q_slot<CQ>(cq, S));
-    if (threadIdx.x < 128) rv = threadIdx.x < 64 ? lse_g[threadIdx.x] : del_g[threadIdx.x - 64];
-    tile_store(qr, smem);
-    tile_store(dr, smem + TILE_BYTES);
-    if (threadIdx.x < 128) rowv[threadIdx.x] = rv;
-    __syncthreads();
-  }
+  wait_vm_all();
 
   // LEAN (a key-length mask, the model's case): the mask term leaves the loop — a masked key's P
   // is computed as if it were live and its dK / dV rows are zeroed once at the end (dK / dV of a
@@ -800,24 +669,11 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
   auto qloop = [&](auto lean_tag) {
   constexpr bool LEAN = decltype(lean_tag)::value;
   for (int qt = 0; qt < nt; ++qt) {
-    const uint8_t* Qs;
-    const float* lse_s;
-    if constexpr (RING) {
-      wait_stages(min(nt - 1 - qt, NBUF - 2), true);
-      __syncthreads();
-      if (qt + NBUF - 1 < nt) issue(qt + NBUF - 1);
-      Qs = smem + (qt % NBUF) * STAGE;
-      lse_s = reinterpret_cast<const float*>(Qs + 2 * TILE_BYTES);
-    } else {
-      Qs = smem + (qt & 1) * 2 * TILE_BYTES;
-      lse_s = rowv + (qt & 1) * 128;
-      if (qt + 1 < nt) {
-        tile_load(qr, Qg, ldq, (qt + 1) * 64, q_slot<CQ>(cq, S));
-        tile_load(dr, dOg, ldo, (qt + 1) * 64, q_slot<CQ>(cq, S));
-        if (threadIdx.x < 128)
-          rv = threadIdx.x < 64 ? lse_g[(qt + 1) * 64 + threadIdx.x] : del_g[(qt + 1) * 64 + threadIdx.x - 64];
-      }
-    }
+    wait_stages(min(nt - 1 - qt, NBUF - 2), true);
+    __syncthreads();
+    if (qt + NBUF - 1 < nt) issue(qt + NBUF - 1);
+    const uint8_t* Qs = smem + (qt % NBUF) * STAGE;
+    const float* lse_s = reinterpret_cast<const float*>(Qs + 2 * TILE_BYTES);
     const uint8_t* Ds = Qs + TILE_BYTES;
     const float* del_s = lse_s + 64;
     if constexpr (CQ) {
@@ -834,81 +690,54 @@ __global__ __launch_bounds__(256, KS == 2 ? 1 : 2) void attn_bwd_dkdv_kernel(
     }
 #pragma unroll
     for (int i2 = 0; i2 < 2; ++i2) {
-      floatx16 sc[KS], dp[KS];
+      floatx16 sc, dp;
 #pragma unroll
-      for (int u = 0; u < KS; ++u)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) { sc[u][i] = 0.f; dp[u][i] = 0.f; }
+      for (int i = 0; i < 16; ++i) { sc[i] = 0.f; dp[i] = 0.f; }
 #pragma unroll
       for (int ks = 0; ks < 4; ++ks) {
         const bf16x8 qfr = lds_row_frag(Qs, 32 * i2 + r, 2 * ks + hh);
         const bf16x8 dfr = lds_row_frag(Ds, 32 * i2 + r, 2 * ks + hh);
 #pragma unroll
-        for (int u = 0; u < KS; ++u) {
-          sc[u] = mfma32(qfr, kf[u][ks], sc[u]);
-          dp[u] = mfma32(dfr, vf[u][ks], dp[u]);
+        for (int u = 0; u < 1; ++u) {  // (one trip: see k above)
+          sc = mfma32(qfr, kf[ks], sc);
+          dp = mfma32(dfr, vf[ks], dp);
         }
       }
 #pragma unroll
-      for (int u = 0; u < KS; ++u)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int qq = 32 * i2 + crow(i, hh);
-          // LEAN: one FMA per score (-lse is a free operand modifier)
-          const float p = __builtin_amdgcn_exp2f(LEAN ? fmaf(sc[u][i], sl2, -lse_s[qq])
-                                                      : sc[u][i] * sl2 + mbk[u] - lse_s[qq]);
-          sc[u][i] = p;
-          dp[u][i] = p * (dp[u][i] - del_s[qq]);
-        }
+      for (int i = 0; i < 16; ++i) {
+        const int qq = 32 * i2 + crow(i, hh);
+        // LEAN: one FMA per score (-lse is a free operand modifier)
+        const float p = __builtin_amdgcn_exp2f(LEAN ? fmaf(sc[i], sl2, -lse_s[qq]) : sc[i] * sl2 + mbk - lse_s[qq]);
+        sc[i] = p;
+        dp[i] = p * (dp[i] - del_s[qq]);
+      }
 #pragma unroll
       for (int ss = 0; ss < 2; ++ss) {
-        bf16x8 pb[KS], db[KS];
-#pragma unroll
-        for (int u = 0; u < KS; ++u) {
-          pb[u] = pack_acc(sc[u], ss);
-          db[u] = pack_acc(dp[u], ss);
-        }
+        const bf16x8 pb = pack_acc(sc, ss), db = pack_acc(dp, ss);
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
           const bf16x8 dtr = tr_operand(Ds, 32 * i2 + 16 * ss, hh, t, lane);
           const bf16x8 qtr = tr_operand(Qs, 32 * i2 + 16 * ss, hh, t, lane);
-#pragma unroll
-          for (int u = 0; u < KS; ++u) {
-            dv[u][t] = mfma32(dtr, pb[u], dv[u][t]);
-            dk[u][t] = mfma32(qtr, db[u], dk[u][t]);
-          }
+          dv[t] = mfma32(dtr, pb, dv[t]);
+          dk[t] = mfma32(qtr, db, dk[t]);
         }
       }
-    }
-    if constexpr (!RING) {
-      if (qt + 1 < nt) {
-        uint8_t* Qn = smem + ((qt & 1) ^ 1) * 2 * TILE_BYTES;
-        tile_store(qr, Qn);
-        tile_store(dr, Qn + TILE_BYTES);
-        if (threadIdx.x < 128) rowv[((qt & 1) ^ 1) * 128 + threadIdx.x] = rv;
-      }
-      __syncthreads();
     }
   }
   };
   if (use_len) {
     qloop(std::true_type{});
+    if (k[0] >= kv_end)
 #pragma unroll
-    for (int u = 0; u < KS; ++u)
-      if (k[u] >= kv_end)
+      for (int t = 0; t < 2; ++t)
 #pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-          for (int i = 0; i < 16; ++i) dk[u][t][i] = dv[u][t][i] = 0.f;
+        for (int i = 0; i < 16; ++i) dk[t][i] = dv[t][i] = 0.f;
   } else {
     qloop(std::false_type{});
   }
-#pragma unroll
-  for (int u = 0; u < KS; ++u) {
-    const bool live = k[u] < S;
-    store_row64(dkv_g + (rb + k[u]) * ldd + (long)H * HD + h * HD, dk[u], scale, hh, live);
-    store_row64(dkv_g + (rb + k[u]) * ldd + 2L * H * HD + h * HD, dv[u], 1.f, hh, live);
-  }
+  const bool live = k[0] < S;
+  store_row64(dkv_g + (rb + k[0]) * ldd + (long)H * HD + h * HD, dk, scale, hh, live);
+  store_row64(dkv_g + (rb + k[0]) * ldd + 2L * H * HD + h * HD, dv, 1.f, hh, live);
 }
 
 // Block order remapped so that the query blocks of one (batch, head) share an XCD's L2 (their K/V
@@ -917,23 +746,35 @@ constexpr int kAttnXcd = 1;
 
 }  // namespace
 
+// the kernels exponentiate with exp2: the softmax scale in log2 units
+static float scale_log2(float scale) { return scale * 1.4426950408889634f; }
+
 // The compact-query instantiations and their entry points are compiled in a translation unit of
 // their own (attention_compact_q.hip, which includes this file for the kernel templates), so that
-// this unit's code object holds exactly the kernels it held before, at the same addresses: the lean
-// forward loop's row maximum (vmax3) reads the score accumulators right behind the MFMA chain, what
-// it sees depends on instruction timing, and moving a kernel inside its code object was measured to
-// change output bits (tests/test_attention_varlen_gpu.py, packed against fixed-S).
+// this unit's code object holds exactly the kernels it held before, at the same addresses: moving a
+// kernel inside its code object was measured to change output bits with unchanged assembly
+// (tests/test_attention_varlen_gpu.py, packed against fixed-S).
+// Read from the disassembly: in the lean forward loop the row maximum's first v_max3_f32 (vmax3,
+// inline asm in dl_attn_tile.h) follows the last MFMA of the score chain it reads with no wait
+// state between them, where an 8-pass MFMA's result needs 12 before a VALU reads it; the compiler
+// pads no hazard for an instruction inside an asm statement (cdna_hip_programming.md 5.7 item 2).
+// The maximum can so be taken from accumulator registers the MFMA has not written yet.  The result
+// stays a valid softmax (the maximum is only the deferred-rescale reference point).  Supposed, not
+// measured: that this is why bits move with a kernel's address and with a row's 32-row sub-block.
+// docs/KERNELS.md ("Compact queries") has the listing; the pad is a change of its own, since it
+// changes output bits.
 #ifndef DL_ATTN_COMPACT_Q_UNIT
+
+// head_dim 64 with 16-byte aligned rows
+static bool hd64_ok(int D, long ld, long ldo) { return D == HD && ld % 8 == 0 && ldo % 8 == 0; }
 
 int dl_attn_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo, float* lse,
                 int B, int H, int S, int D, float scale, hipStream_t st) {
   if (D == 128) return dl_attn_hd128_fwd(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, scale, st);
-  if (D != HD || S % 64 != 0 || ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  // 4 waves x 2 query sub-blocks of 32 rows per wave, K/V staged by the LDS-DMA ring (it frees the
-  // 16 staging VGPRs the second sub-block needs); 8-wave blocks measured 5% slower (round 2)
+  if (!hd64_ok(D, ld, ldo) || S % 64 != 0) return -1;
   dim3 grid((S + 255) / 256, H, B);
-  attn_fwd_kernel<true, 2><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, sl2, kAttnXcd);
+  attn_fwd_kernel<false><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, scale_log2(scale),
+                                               kAttnXcd);
   return 0;
 }
 
@@ -942,50 +783,50 @@ int dl_attn_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinf
                 int S, int D, float scale, hipStream_t st) {
   if (D == 128)
     return dl_attn_hd128_bwd(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, H, S, scale, st);
-  if (D != HD || S % 64 != 0 || ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  // dQ: 2 query sub-blocks per wave with the LDS-DMA ring; dK/dV: one key sub-block per wave, also
-  // through the ring (3.5% faster than register staging at B = 512; the one-wave-per-SIMD
-  // 2-sub-block form measured 8% slower: profiles/README.md)
+  if (!hd64_ok(D, ld, ldo) || S % 64 != 0) return -1;
+  const float sl2 = scale_log2(scale);
   dim3 grid_dq((S + 255) / 256, H, B);
-  attn_bwd_dq_kernel<true, 2><<<grid_dq, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv,
-                                                       dbias, B, H, S, sl2, scale, kAttnXcd);
+  attn_bwd_dq_kernel<false><<<grid_dq, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B,
+                                                     H, S, sl2, scale, kAttnXcd);
   dim3 grid_kv((S + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<true, 1><<<grid_kv, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H,
-                                                         S, sl2, scale, kAttnXcd);
+  attn_bwd_dkdv_kernel<false><<<grid_kv, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H, S,
+                                                       sl2, scale, kAttnXcd);
   return 0;
 }
 
 // Packed (variable-length) batches: seqinfo = int32[2B + 1] (row offsets, then key lengths), lse /
 // delta [H, T]; max_slot (the largest slot, host side) sizes the grids.  The callers validate the
 // layout contract (csrc/bindings.cpp).
+static bool packed_ok(const int* seqinfo, int B, int T, int max_slot) {
+  return seqinfo && B >= 1 && T % 64 == 0 && max_slot >= 64 && max_slot % 64 == 0 && max_slot <= T;
+}
+
 int dl_attn_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B, int T,
                        int max_slot, int H, int D, float scale, hipStream_t st) {
-  if (!seqinfo || B < 1 || T % 64 != 0 || max_slot < 64 || max_slot % 64 != 0 || max_slot > T) return -1;
+  if (!packed_ok(seqinfo, B, T, max_slot)) return -1;
   if (D == 128) return dl_attn_hd128_varlen_fwd(qkv, ld, seqinfo, out, ldo, lse, B, T, max_slot, H, scale, st);
-  if (D != HD || ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
+  if (!hd64_ok(D, ld, ldo)) return -1;
   dim3 grid((max_slot + 255) / 256, H, B);
-  attn_fwd_kernel<true, 2, 4, true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, ldo, lse, B, H, T, sl2,
-                                                          kAttnXcd);
+  attn_fwd_kernel<true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, ldo, lse, B, H, T, scale_log2(scale),
+                                              kAttnXcd);
   return 0;
 }
 
 int dl_attn_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout, long ldo,
                        const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T, int max_slot, int H,
                        int D, float scale, hipStream_t st) {
-  if (!seqinfo || B < 1 || T % 64 != 0 || max_slot < 64 || max_slot % 64 != 0 || max_slot > T) return -1;
+  if (!packed_ok(seqinfo, B, T, max_slot)) return -1;
   if (D == 128)
     return dl_attn_hd128_varlen_bwd(qkv, ld, seqinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, T, max_slot, H, scale,
                                     st);
-  if (D != HD || ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
+  if (!hd64_ok(D, ld, ldo)) return -1;
+  const float sl2 = scale_log2(scale);
   dim3 grid_dq((max_slot + 255) / 256, H, B);
-  attn_bwd_dq_kernel<true, 2, true><<<grid_dq, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, dout, ldo, lse, delta,
-                                                             dqkv, dbias, B, H, T, sl2, scale, kAttnXcd);
+  attn_bwd_dq_kernel<true><<<grid_dq, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, dout, ldo, lse, delta, dqkv, dbias,
+                                                    B, H, T, sl2, scale, kAttnXcd);
   dim3 grid_kv((max_slot + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<true, 1, true><<<grid_kv, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv,
-                                                               B, H, T, sl2, scale, kAttnXcd);
+  attn_bwd_dkdv_kernel<true><<<grid_kv, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv, B, H, T,
+                                                      sl2, scale, kAttnXcd);
   return 0;
 }
 
@@ -1003,11 +844,10 @@ static bool compact_q_ok(const void* q, const void* kv, const int* qcnt, int B, 
 int dl_attn_fwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
                   bf16_t* out, long ldo, float* lse, int B, int H, int S, int Sq, int D, float scale, hipStream_t st) {
   if (!compact_q_ok(q, kv, qcnt, B, H, S, Sq, D, ld, ldo)) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
   const CompactQ cq{q, nullptr, nullptr, 0, qcnt, Sq};
   dim3 grid((Sq + 255) / 256, H, B);
-  attn_fwd_kernel<true, 2, 4, false, CompactQ><<<grid, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, sl2,
-                                                                 kAttnXcd, cq);
+  attn_fwd_kernel<false, CompactQ><<<grid, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, ldo, lse, B, H, S,
+                                                         scale_log2(scale), kAttnXcd, cq);
   return 0;
 }
 
@@ -1015,14 +855,14 @@ int dl_attn_bwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias
                   const bf16_t* out, const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dq,
                   bf16_t* dkv, float* dbias, int B, int H, int S, int Sq, int D, float scale, hipStream_t st) {
   if (!compact_q_ok(q, kv, qcnt, B, H, S, Sq, D, ld, ldo) || !dq || !dkv) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
+  const float sl2 = scale_log2(scale);
   const CompactQ cq{q, dq, dkv, 2L * H * HD, qcnt, Sq};
   dim3 grid_dq((Sq + 255) / 256, H, B);
-  attn_bwd_dq_kernel<true, 2, false, CompactQ><<<grid_dq, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, dout, ldo, lse, delta,
-                                                                    nullptr, dbias, B, H, S, sl2, scale, kAttnXcd, cq);
+  attn_bwd_dq_kernel<false, CompactQ><<<grid_dq, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, dout, ldo, lse, delta,
+                                                               nullptr, dbias, B, H, S, sl2, scale, kAttnXcd, cq);
   dim3 grid_kv((S + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<true, 1, false, CompactQ><<<grid_kv, 256, 0, st>>>(kv, ld, mbias, kvinfo, dout, ldo, lse, delta,
-                                                                      nullptr, B, H, S, sl2, scale, kAttnXcd, cq);
+  attn_bwd_dkdv_kernel<false, CompactQ><<<grid_kv, 256, 0, st>>>(kv, ld, mbias, kvinfo, dout, ldo, lse, delta, nullptr,
+                                                                 B, H, S, sl2, scale, kAttnXcd, cq);
   return 0;
 }
 
