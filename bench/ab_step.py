@@ -1,8 +1,8 @@
 """Same-process A/B of ALBERT-large micro-step variants (cdna_hip_programming.md §5.4 rule 24:
 interleaved rounds in ONE process; box-to-box spread on this pool is up to ~10%).
 
-    python bench/ab_step.py --batch 256 --ab residual     # residual add in GEMM epilogue vs in LayerNorm
     python bench/ab_step.py --batch 256 --ab dgradwt      # dgrad GEMMs on transposed weight copies
+    python bench/ab_step.py --batch 256 --ab sharedwgrad  # weight-gradient slabs summed once per micro-step
 """
 import argparse
 import json
@@ -19,9 +19,7 @@ from bench.model_step import synthetic  # noqa: E402
 
 
 def set_variant(ab, v):
-    if ab == "residual":
-        albert._RESIDUAL_IN_GEMM = v == "B"
-    elif ab == "sharedwgrad":  # shared-layer weight-gradient slabs summed once per micro-step (B)
+    if ab == "sharedwgrad":  # shared-layer weight-gradient slabs summed once per micro-step (B)
         albert._SHARED_WGRAD = v == "B"
     elif ab == "dgradwt":  # dgrad GEMMs against transposed weight copies (B) vs the plain weights (A)
         albert._DGRAD_WT = v == "B"
@@ -35,7 +33,7 @@ def main():
     ap.add_argument("--seq", type=int, default=512)
     ap.add_argument("--iters", type=int, default=4)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--ab", default="residual")
+    ap.add_argument("--ab", default="dgradwt")
     args = ap.parse_args()
     dev = torch.device("cuda")
     cfg = albert.AlbertConfig.albert_large_v2()

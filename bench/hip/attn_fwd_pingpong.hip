@@ -1,7 +1,8 @@
 // Round-5 experiment, NOT built: the 8-wave ping-pong attention forward (measured 13% slower than
 // the shipped 4-wave kernel at B=512, S=512, d=64: profiles/r5_attn_fwd_pingpong_negative.jsonl).
 // It was compiled inside dedloc_amd/csrc/kernels/attention.hip (helpers FwdCtx, vmax3, half_max,
-// tr_operand, lds_row_frag, wait_stages, STAGE, ... live there) and dispatched from dl_attn_fwd with
+// tr_operand, lds_row_frag, wait_stages, STAGE, ... live there) and dispatched from its forward
+// entry point (today dl_attn_hd64_fwd over a DlAttn; positional arguments then) with
 //   dim3 gp((S + PP_Q - 1) / PP_Q, H, B);
 //   attn_fwd_pp_kernel<0><<<gp, 512, 0, st>>>(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, sl2, 1);
 // Template PRIO: 0 = groups w >> 2 (waves w and w + 4 share a SIMD), 1 = groups w & 1 (slower

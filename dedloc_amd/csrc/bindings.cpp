@@ -482,6 +482,8 @@ std::tuple<at::Tensor, at::Tensor> knn_vote(const at::Tensor& vals, const at::Te
 }
 
 // ------------------------------------------------------------------ attention
+// Every fused call is one DlAttn descriptor (dl_kernels.h) handed to attn_route below, the only
+// place that calls the launchers of attention.hip, attention_compact_q.hip and attention_hd128.hip.
 inline const int* kvinfo_ptr(const c10::optional<at::Tensor>& kvinfo, int64_t B) {
   if (!kvinfo.has_value()) return nullptr;
   expect(*kvinfo, at::kInt, "kvinfo");
@@ -489,61 +491,92 @@ inline const int* kvinfo_ptr(const c10::optional<at::Tensor>& kvinfo, int64_t B)
   return kvinfo->data_ptr<int>();
 }
 
-// the fused kernels exist for these head sizes only (ops.FUSED_HEAD_DIMS); every other size goes
-// through ops.attn_composed_*
-inline void check_head_dim(int64_t D, int64_t ld, int64_t H, const char* what) {
-  TORCH_CHECK((D == 64 || D == 128) && ld == 3 * H * D, "dedloc_amd: ", what, ": head_dim ", D, " (row length ", ld,
-              ", ", H, " heads) is not supported by the fused attention kernels; supported head sizes are 64 and 128");
+// an optional fp32 tensor of n values (mbias [B, S], dbias [3*H*D]): its data, or null without one
+inline float* opt_f32(const c10::optional<at::Tensor>& t, int64_t n, const char* name, const char* shape,
+                      const char* what) {
+  if (!t.has_value()) return nullptr;
+  expect(*t, at::kFloat, name);
+  TORCH_CHECK(t->numel() == n, what, ": ", name, " must be ", shape);
+  return f32(*t);
+}
+
+// the fixed-S mask of a descriptor whose B and S are set
+inline void fixed_mask(DlAttn& a, const c10::optional<at::Tensor>& mbias, const c10::optional<at::Tensor>& kvinfo,
+                       const char* what) {
+  a.mbias = opt_f32(mbias, (int64_t)a.B * a.S, "mbias", "[B, S]", what);
+  a.kvinfo = kvinfo_ptr(kvinfo, a.B);
+}
+
+// The one place an attention kernel is chosen: head_dim 128 runs in attention_hd128.hip, head_dim
+// 64 in attention.hip or, with compact queries, in attention_compact_q.hip.  There are no other
+// fused kernels (ops.FUSED_HEAD_DIMS): every other head size goes through ops.attn_composed_*.
+void attn_route(const DlAttn& a, bool bwd, const char* what, hipStream_t st) {
+  if (a.q) {
+    TORCH_CHECK(a.D == 64 && !a.seqinfo, "dedloc_amd: ", what,
+                ": compact queries exist for head_dim 64 only, on the fixed-S layout");
+    return check(bwd ? dl_attn_hd64q_bwd(a, st) : dl_attn_hd64q_fwd(a, st), what);
+  }
+  TORCH_CHECK((a.D == 64 || a.D == 128) && a.ld == 3L * a.H * a.D, "dedloc_amd: ", what, ": head_dim ", a.D,
+              " (row length ", a.ld, ", ", a.H,
+              " heads) is not supported by the fused attention kernels; supported head sizes are 64 and 128");
+  if (a.D == 128) return check(bwd ? dl_attn_hd128_bwd(a, st) : dl_attn_hd128_fwd(a, st), what);
+  check(bwd ? dl_attn_hd64_bwd(a, st) : dl_attn_hd64_fwd(a, st), what);
+}
+
+// the fused QKV buffer [rows, 3*H*D] of the forms without compact queries (attn_route checks the
+// head size it implies) and the context's row length
+inline DlAttn qkv_desc(const at::Tensor& qkv, int64_t H, double scale) {
+  expect(qkv, at::kBFloat16, "qkv");
+  DlAttn a;
+  a.kv = cbf(qkv), a.ld = qkv.size(-1);
+  a.H = (int)H, a.D = (int)(a.ld / (3 * H)), a.scale = (float)scale;
+  a.ldo = H * a.D;
+  return a;
+}
+
+// the backward's out / dout (`ctx` values each) and lse (`stats` values), as the forward returned them
+inline void bwd_inputs(DlAttn& a, const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse, int64_t ctx,
+                       int64_t stats, const char* what, const char* shapes) {
+  expect(out, at::kBFloat16, "out");
+  expect(dout, at::kBFloat16, "dout");
+  expect(lse, at::kFloat, "lse");
+  TORCH_CHECK(out.numel() == ctx && dout.numel() == ctx && lse.numel() == stats, what, ": out / dout must be ", shapes);
+  a.out = bf(out), a.dout = cbf(dout), a.lse = f32(lse);
 }
 
 std::tuple<at::Tensor, at::Tensor> attn_fwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& mbias, int64_t H,
                                             int64_t S, double scale, const c10::optional<at::Tensor>& kvinfo) {
-  expect(qkv, at::kBFloat16, "qkv");
-  const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H), B = T / S;
-  check_head_dim(D, ld, H, "attn_fwd");
-  auto out = at::empty({T, H * D}, qkv.options());
+  DlAttn a = qkv_desc(qkv, H, scale);
+  const int64_t T = qkv.numel() / a.ld, B = T / S;
+  auto out = at::empty({T, a.ldo}, qkv.options());
   auto lse = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
-  const float* mb = nullptr;
-  if (mbias.has_value()) {
-    expect(*mbias, at::kFloat, "mbias");
-    mb = f32(*mbias);
-  }
-  check(dl_attn_fwd(cbf(qkv), ld, mb, kvinfo_ptr(kvinfo, B), bf(out), H * D, f32(lse), (int)B, (int)H, (int)S,
-                    (int)D, (float)scale, cur_stream(qkv)),
-        "attn_fwd");
+  a.B = (int)B, a.S = (int)S;
+  fixed_mask(a, mbias, kvinfo, "attn_fwd");
+  a.out = bf(out), a.lse = f32(lse);
+  attn_route(a, false, "attn_fwd", cur_stream(qkv));
   return {out, lse};
 }
 
 at::Tensor attn_bwd(const at::Tensor& qkv, const c10::optional<at::Tensor>& mbias, const at::Tensor& out,
                     const at::Tensor& dout, const at::Tensor& lse, int64_t H, int64_t S, double scale,
                     const c10::optional<at::Tensor>& kvinfo, const c10::optional<at::Tensor>& dbias) {
-  expect(qkv, at::kBFloat16, "qkv");
-  expect(out, at::kBFloat16, "out");
-  expect(dout, at::kBFloat16, "dout");
-  const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H), B = T / S;
-  check_head_dim(D, ld, H, "attn_bwd");
+  DlAttn a = qkv_desc(qkv, H, scale);
+  const int64_t T = qkv.numel() / a.ld, B = T / S;
+  bwd_inputs(a, out, dout, lse, T * a.ldo, B * H * S, "attn_bwd", "[B*S, H*D] and lse [B, H, S]");
   auto dqkv = at::empty_like(qkv);
   auto delta = at::empty({B, H, S}, qkv.options().dtype(at::kFloat));
-  const float* mb = mbias.has_value() ? f32(*mbias) : nullptr;
-  float* dbp = nullptr;
-  if (dbias.has_value()) {
-    expect(*dbias, at::kFloat, "dbias");
-    TORCH_CHECK(dbias->numel() == ld, "dbias must have 3*H*D elements");
-    dbp = f32(*dbias);
-  }
-  check(dl_attn_bwd(cbf(qkv), ld, mb, kvinfo_ptr(kvinfo, B), cbf(out), cbf(dout), H * D, f32(lse), f32(delta),
-                    bf(dqkv), dbp, (int)B, (int)H, (int)S, (int)D, (float)scale, cur_stream(qkv)),
-        "attn_bwd");
+  a.B = (int)B, a.S = (int)S;
+  fixed_mask(a, mbias, kvinfo, "attn_bwd");
+  a.delta = f32(delta), a.dqkv = bf(dqkv);
+  a.dbias = opt_f32(dbias, a.ld, "dbias", "3*H*D values", "attn_bwd");
+  attn_route(a, true, "attn_bwd", cur_stream(qkv));
   return dqkv;
 }
 
 // Compact queries: q [B*Sq, H*64] holds sequence b's queries in the first qcnt[b] rows of its slot of
 // Sq rows; kv [B*S, 2*H*64] (K | V) may be a column slice of the fused QKV buffer (any row stride).
-struct CompactLayout {
-  int64_t B, Sq, D, ld;
-};
-inline CompactLayout compact_layout(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt, int64_t H,
-                                    int64_t S, const char* what) {
+inline DlAttn compact_layout(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt, int64_t H, int64_t S,
+                             double scale, const char* what) {
   expect(q, at::kBFloat16, "q");
   expect(qcnt, at::kInt, "qcnt");
   TORCH_CHECK(kv.is_cuda() && kv.scalar_type() == at::kBFloat16 && kv.dim() == 2 && kv.stride(1) == 1, what,
@@ -560,25 +593,23 @@ inline CompactLayout compact_layout(const at::Tensor& q, const at::Tensor& kv, c
   TORCH_CHECK(Sq >= 64 && Sq % 64 == 0 && Sq <= S, what, ": the query slot Sq = ", Sq,
               " must be a multiple of 64 in 64 .. S = ", S);
   TORCH_CHECK(qcnt.numel() == B, what, ": qcnt must be int32[B]");
-  return CompactLayout{B, Sq, D, ld};
+  DlAttn a;
+  a.kv = reinterpret_cast<const bf16_t*>(kv.data_ptr()), a.ld = ld;
+  a.q = cbf(q), a.qcnt = qcnt.data_ptr<int>(), a.Sq = (int)Sq;
+  a.B = (int)B, a.H = (int)H, a.S = (int)S, a.D = (int)D, a.scale = (float)scale;
+  a.ldo = H * D;
+  return a;
 }
 
 std::tuple<at::Tensor, at::Tensor> attn_fwd_q(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt,
                                               const c10::optional<at::Tensor>& mbias, int64_t H, int64_t S,
                                               double scale, const c10::optional<at::Tensor>& kvinfo) {
-  const CompactLayout L = compact_layout(q, kv, qcnt, H, S, "attn_fwd_q");
-  auto out = at::empty({L.B * L.Sq, H * L.D}, q.options());
-  auto lse = at::empty({L.B, H, L.Sq}, q.options().dtype(at::kFloat));
-  const float* mb = nullptr;
-  if (mbias.has_value()) {
-    expect(*mbias, at::kFloat, "mbias");
-    TORCH_CHECK(mbias->numel() == L.B * S, "attn_fwd_q: mbias must be [B, S]");
-    mb = f32(*mbias);
-  }
-  check(dl_attn_fwd_q(cbf(q), reinterpret_cast<const bf16_t*>(kv.data_ptr()), L.ld, mb, kvinfo_ptr(kvinfo, L.B),
-                      qcnt.data_ptr<int>(), bf(out), H * L.D, f32(lse), (int)L.B, (int)H, (int)S, (int)L.Sq, (int)L.D,
-                      (float)scale, cur_stream(q)),
-        "attn_fwd_q");
+  DlAttn a = compact_layout(q, kv, qcnt, H, S, scale, "attn_fwd_q");
+  fixed_mask(a, mbias, kvinfo, "attn_fwd_q");
+  auto out = at::empty({(int64_t)a.B * a.Sq, a.ldo}, q.options());
+  auto lse = at::empty({a.B, H, a.Sq}, q.options().dtype(at::kFloat));
+  a.out = bf(out), a.lse = f32(lse);
+  attn_route(a, false, "attn_fwd_q", cur_stream(q));
   return {out, lse};
 }
 
@@ -591,43 +622,23 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_bwd_q(const at::Tensor& q, c
                                                           const at::Tensor& lse, int64_t H, int64_t S, double scale,
                                                           const c10::optional<at::Tensor>& kvinfo,
                                                           const c10::optional<at::Tensor>& dbias) {
-  const CompactLayout L = compact_layout(q, kv, qcnt, H, S, "attn_bwd_q");
-  expect(out, at::kBFloat16, "out");
-  expect(dout, at::kBFloat16, "dout");
-  expect(lse, at::kFloat, "lse");
-  TORCH_CHECK(out.numel() == q.numel() && dout.numel() == q.numel() && lse.numel() == L.B * H * L.Sq,
-              "attn_bwd_q: out / dout must be [B*Sq, H*D] and lse [B, H, Sq]");
+  DlAttn a = compact_layout(q, kv, qcnt, H, S, scale, "attn_bwd_q");
+  fixed_mask(a, mbias, kvinfo, "attn_bwd_q");
+  bwd_inputs(a, out, dout, lse, q.numel(), (int64_t)a.B * H * a.Sq, "attn_bwd_q", "[B*Sq, H*D] and lse [B, H, Sq]");
   auto dq = at::empty_like(q);
-  auto dkv = at::empty({L.B * S, 2 * H * L.D}, q.options());
-  auto delta = at::empty({L.B, H, L.Sq}, q.options().dtype(at::kFloat));
-  const float* mb = nullptr;
-  if (mbias.has_value()) {
-    expect(*mbias, at::kFloat, "mbias");
-    TORCH_CHECK(mbias->numel() == L.B * S, "attn_bwd_q: mbias must be [B, S]");
-    mb = f32(*mbias);
-  }
-  float* dbp = nullptr;
-  if (dbias.has_value()) {
-    expect(*dbias, at::kFloat, "dbias");
-    TORCH_CHECK(dbias->numel() == 3 * H * L.D, "dbias must have 3*H*D elements");
-    dbp = f32(*dbias);
-  }
-  check(dl_attn_bwd_q(cbf(q), reinterpret_cast<const bf16_t*>(kv.data_ptr()), L.ld, mb, kvinfo_ptr(kvinfo, L.B),
-                      qcnt.data_ptr<int>(), cbf(out), cbf(dout), H * L.D, f32(lse), f32(delta), bf(dq), bf(dkv), dbp,
-                      (int)L.B, (int)H, (int)S, (int)L.Sq, (int)L.D, (float)scale, cur_stream(q)),
-        "attn_bwd_q");
+  auto dkv = at::empty({(int64_t)a.B * S, 2 * a.ldo}, q.options());
+  auto delta = at::empty({a.B, H, a.Sq}, q.options().dtype(at::kFloat));
+  a.delta = f32(delta), a.dq = bf(dq), a.dkv = bf(dkv);
+  a.dbias = opt_f32(dbias, 3 * a.ldo, "dbias", "3*H*D values", "attn_bwd_q");
+  attn_route(a, true, "attn_bwd_q", cur_stream(q));
   return {dq, dkv, delta};
 }
 
 // Packed variable-length batches.  seqinfo (device) = int32[2B + 1]: B + 1 row offsets, then B key
 // lengths; seqinfo_host is the same array in host memory — the layout contract is checked on it, so
 // a call costs no device synchronisation, and the largest slot (the grids' x extent) is read from it.
-struct PackedLayout {
-  int64_t B, T, max_slot;
-  const int* dev;
-};
-inline PackedLayout packed_layout(const at::Tensor& seqinfo, const at::Tensor& seqinfo_host, int64_t T,
-                                  const char* what) {
+inline void packed_layout(DlAttn& a, const at::Tensor& seqinfo, const at::Tensor& seqinfo_host, int64_t T,
+                          const char* what) {
   expect(seqinfo, at::kInt, "seqinfo");
   TORCH_CHECK(seqinfo_host.device().is_cpu() && seqinfo_host.scalar_type() == at::kInt && seqinfo_host.is_contiguous(),
               what, ": seqinfo_host must be a contiguous int32 CPU tensor");
@@ -648,46 +659,33 @@ inline PackedLayout packed_layout(const at::Tensor& seqinfo, const at::Tensor& s
                 slot, " rows");
     max_slot = std::max(max_slot, slot);
   }
-  return PackedLayout{B, T, max_slot, seqinfo.data_ptr<int>()};
+  a.seqinfo = seqinfo.data_ptr<int>(), a.B = (int)B, a.T = (int)T, a.max_slot = (int)max_slot;
 }
 
 std::tuple<at::Tensor, at::Tensor> attn_varlen_fwd(const at::Tensor& qkv, const at::Tensor& seqinfo,
                                                    const at::Tensor& seqinfo_host, int64_t H, double scale) {
-  expect(qkv, at::kBFloat16, "qkv");
-  const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H);
-  check_head_dim(D, ld, H, "attn_varlen_fwd");
-  const PackedLayout L = packed_layout(seqinfo, seqinfo_host, T, "attn_varlen_fwd");
-  auto out = at::empty({T, H * D}, qkv.options());
+  DlAttn a = qkv_desc(qkv, H, scale);
+  const int64_t T = qkv.numel() / a.ld;
+  packed_layout(a, seqinfo, seqinfo_host, T, "attn_varlen_fwd");
+  auto out = at::empty({T, a.ldo}, qkv.options());
   auto lse = at::empty({H, T}, qkv.options().dtype(at::kFloat));
-  check(dl_attn_varlen_fwd(cbf(qkv), ld, L.dev, bf(out), H * D, f32(lse), (int)L.B, (int)T, (int)L.max_slot, (int)H,
-                           (int)D, (float)scale, cur_stream(qkv)),
-        "attn_varlen_fwd");
+  a.out = bf(out), a.lse = f32(lse);
+  attn_route(a, false, "attn_varlen_fwd", cur_stream(qkv));
   return {out, lse};
 }
 
 at::Tensor attn_varlen_bwd(const at::Tensor& qkv, const at::Tensor& seqinfo, const at::Tensor& seqinfo_host,
                            const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse, int64_t H,
                            double scale, const c10::optional<at::Tensor>& dbias) {
-  expect(qkv, at::kBFloat16, "qkv");
-  expect(out, at::kBFloat16, "out");
-  expect(dout, at::kBFloat16, "dout");
-  expect(lse, at::kFloat, "lse");
-  const int64_t ld = qkv.size(-1), T = qkv.numel() / ld, D = ld / (3 * H);
-  check_head_dim(D, ld, H, "attn_varlen_bwd");
-  const PackedLayout L = packed_layout(seqinfo, seqinfo_host, T, "attn_varlen_bwd");
-  TORCH_CHECK(out.numel() == T * H * D && dout.numel() == T * H * D && lse.numel() == H * T,
-              "attn_varlen_bwd: out / dout must be [T, H*D] and lse [H, T]");
+  DlAttn a = qkv_desc(qkv, H, scale);
+  const int64_t T = qkv.numel() / a.ld;
+  packed_layout(a, seqinfo, seqinfo_host, T, "attn_varlen_bwd");
+  bwd_inputs(a, out, dout, lse, T * a.ldo, H * T, "attn_varlen_bwd", "[T, H*D] and lse [H, T]");
   auto dqkv = at::empty_like(qkv);
   auto delta = at::empty({H, T}, qkv.options().dtype(at::kFloat));
-  float* dbp = nullptr;
-  if (dbias.has_value()) {
-    expect(*dbias, at::kFloat, "dbias");
-    TORCH_CHECK(dbias->numel() == ld, "dbias must have 3*H*D elements");
-    dbp = f32(*dbias);
-  }
-  check(dl_attn_varlen_bwd(cbf(qkv), ld, L.dev, cbf(out), cbf(dout), H * D, f32(lse), f32(delta), bf(dqkv), dbp,
-                           (int)L.B, (int)T, (int)L.max_slot, (int)H, (int)D, (float)scale, cur_stream(qkv)),
-        "attn_varlen_bwd");
+  a.delta = f32(delta), a.dqkv = bf(dqkv);
+  a.dbias = opt_f32(dbias, a.ld, "dbias", "3*H*D values", "attn_varlen_bwd");
+  attn_route(a, true, "attn_varlen_bwd", cur_stream(qkv));
   return dqkv;
 }
 

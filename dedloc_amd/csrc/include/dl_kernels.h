@@ -152,6 +152,50 @@ struct DlGemm {
 int dl_gemm8(const DlGemm& g, hipStream_t st);
 int dl_gemm(const DlGemm& g, hipStream_t st);
 
+// One fused flash-attention call, forward or backward (bf16 in / out, fp32 softmax state).  Which
+// form it is follows from the pointers that are set: `seqinfo` selects the packed layout, `q` the
+// compact queries; neither is the fixed-S form over the fused QKV buffer.
+struct DlAttn {
+  // Keys / values: the fused QKV buffer [rows, ld] (Q | K | V, head h at columns h*D of each third;
+  // rows = B*S, packed: T), which then holds the queries too; with compact queries K's first column
+  // in the [B*S, ld] key / value buffer (V starts H*D columns after it).  Rows are 16-byte aligned.
+  const bf16_t* kv = nullptr; long ld = 0;
+  // Compact queries (head_dim 64, fixed-S layout): sequence b's queries are the first qcnt[b] rows of
+  // its slot of Sq rows (Sq % 64 == 0, 64 <= Sq <= S) in q [B*Sq, ldo]; out / dout / dq share that
+  // layout, lse / delta are [B, H, Sq]; dkv is [B*S, 2*H*D] (dK | dV, all keys).  Slot rows past
+  // qcnt[b] are dead: clamped on load, absent from lse / delta, dK / dV and the bias gradients, and
+  // stored as zeros in out / dq.  dq and dkv are the backward's outputs in place of dqkv.
+  const bf16_t* q = nullptr; const int* qcnt = nullptr; int Sq = 0;
+  bf16_t* dq = nullptr; bf16_t* dkv = nullptr;
+  // Fixed-S mask (both optional): mbias fp32 [B, S], the additive key bias; kvinfo int32[B + 1], the
+  // key lengths and an "every row of mbias is such a prefix mask" flag (padded key tiles are skipped)
+  const float* mbias = nullptr; const int* kvinfo = nullptr;
+  // Packed variable-length batches: seqinfo = int32[2B + 1] = B + 1 row offsets (multiples of 64,
+  // seqinfo[B] == T) then B key lengths (1 <= len <= slot); lse / delta are [H, T]; max_slot is the
+  // largest slot (it sizes the grids).  Same kernels, compiled with the packed row mapping.
+  const int* seqinfo = nullptr; int T = 0, max_slot = 0;
+  int B = 0, H = 0, S = 0, D = 0;  // S % 64 == 0 (unused when packed); D is 64 or 128
+  float scale = 0.f;               // softmax scale (the kernels exponentiate with exp2: scale_log2)
+  float scale_log2() const { return scale * 1.4426950408889634f; }
+  // context [rows, ldo] (head h at columns h*D) and the softmax statistics [B, H, S]: written by the
+  // forward, read by the backward
+  bf16_t* out = nullptr; long ldo = 0; float* lse = nullptr;
+  // Backward: dout in out's layout; delta (scratch, shaped as lse); dqkv in the QKV buffer's layout;
+  // dbias (optional, fp32 [3 H D], accumulated): the QKV projection's bias gradient (query: column
+  // sums of dQ; key: zero; value: column sums of dout)
+  const bf16_t* dout = nullptr; float* delta = nullptr; bf16_t* dqkv = nullptr; float* dbias = nullptr;
+};
+
+// attention.hip (head_dim 64: fixed-S and packed), attention_compact_q.hip (head_dim 64 with compact
+// queries), attention_hd128.hip (head_dim 128: fixed-S and packed).  Each checks what its kernels
+// need and returns -1 for any other call; csrc/bindings.cpp (attn_route) picks the unit.
+int dl_attn_hd64_fwd(const DlAttn& a, hipStream_t st);
+int dl_attn_hd64_bwd(const DlAttn& a, hipStream_t st);
+int dl_attn_hd64q_fwd(const DlAttn& a, hipStream_t st);
+int dl_attn_hd64q_bwd(const DlAttn& a, hipStream_t st);
+int dl_attn_hd128_fwd(const DlAttn& a, hipStream_t st);
+int dl_attn_hd128_bwd(const DlAttn& a, hipStream_t st);
+
 // swav.hip
 int dl_sinkhorn_ws(int n, int K);
 int dl_sinkhorn(const float* scores, float* Q, float* ws, int n, int K, int bs, float eps, int iters,
@@ -245,45 +289,6 @@ int dl_attn_softmax_fwd(const float* s, const float* mbias, bf16_t* p, float* ls
                         hipStream_t st);
 int dl_attn_softmax_bwd(const float* s, const float* dp, const float* mbias, const float* lse, const float* delta,
                         bf16_t* p, bf16_t* ds, long rows, int H, int S, float c, float scale, hipStream_t st);
-
-// attention.hip: head_dim 64 kernels and the entry points, which send D == 128 to
-// attention_hd128.hip (dl_attn_hd128_*: same arguments, same checks, D fixed).  -1 for any other D.
-int dl_attn_hd128_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo,
-                      float* lse, int B, int H, int S, float scale, hipStream_t st);
-int dl_attn_hd128_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, const bf16_t* out,
-                      const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B,
-                      int H, int S, float scale, hipStream_t st);
-int dl_attn_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo, float* lse,
-                int B, int H, int S, int D, float scale, hipStream_t st);
-// dbias (optional, fp32 [3 H D], accumulated): the QKV projection's bias gradient (query: column
-// sums of dQ; key: zero; value: column sums of dout)
-int dl_attn_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, const bf16_t* out,
-                const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int H,
-                int S, int D, float scale, hipStream_t st);
-// Compact queries (head_dim 64, fixed-S layout): sequence b's queries are the first qcnt[b] rows of its
-// slot of Sq rows (Sq % 64 == 0, 64 <= Sq <= S) in q [B*Sq, ldo]; out / dout / dq share that layout,
-// lse / delta are [B, H, Sq].  kv points at K's first column in the [B*S, ld] key / value buffer (V
-// starts H*64 columns after it); dkv is [B*S, 2*H*64] (dK | dV, all keys).  Slot rows past qcnt[b]
-// are dead: clamped on load, absent from lse / delta, dK / dV and the bias gradients, and stored as
-// zeros in out / dq.  -1 for any other D.
-int dl_attn_fwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
-                  bf16_t* out, long ldo, float* lse, int B, int H, int S, int Sq, int D, float scale, hipStream_t st);
-int dl_attn_bwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
-                  const bf16_t* out, const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dq,
-                  bf16_t* dkv, float* dbias, int B, int H, int S, int Sq, int D, float scale, hipStream_t st);
-// Packed variable-length batches: seqinfo = int32[2B + 1] = B + 1 row offsets (multiples of 64,
-// seqinfo[B] == T) then B key lengths (1 <= len <= slot); lse / delta are [H, T]; max_slot is the
-// largest slot (it sizes the grids).  Same kernels as above, compiled with the packed row mapping.
-int dl_attn_hd128_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B,
-                             int T, int max_slot, int H, float scale, hipStream_t st);
-int dl_attn_hd128_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout,
-                             long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T,
-                             int max_slot, int H, float scale, hipStream_t st);
-int dl_attn_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B, int T,
-                       int max_slot, int H, int D, float scale, hipStream_t st);
-int dl_attn_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout, long ldo,
-                       const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T, int max_slot, int H,
-                       int D, float scale, hipStream_t st);
 
 // pool.hip (SwAV trunk pools and head normalisation; channels-last bf16, C % 8 == 0)
 int dl_maxpool_fwd(const bf16_t* x, bf16_t* y, uint8_t* arg, int N, int H, int W, int C, int P, int Q, hipStream_t st);

@@ -1,5 +1,5 @@
 // Flash-style multi-head self-attention for ALBERT: head_dim 64 (head_dim 128:
-// attention_hd128.hip, reached through the entry points at the end of this file), S % 64 == 0,
+// attention_hd128.hip; csrc/bindings.cpp picks the file by head size), S % 64 == 0,
 // additive key-padding bias, bf16 in/out, fp32 softmax state, never materialises [B,H,S,S].
 //
 // Inputs come straight from the fused QKV projection: qkv is [B*S, 3*H*64] (Q | K | V, head h at
@@ -746,9 +746,6 @@ constexpr int kAttnXcd = 1;
 
 }  // namespace
 
-// the kernels exponentiate with exp2: the softmax scale in log2 units
-static float scale_log2(float scale) { return scale * 1.4426950408889634f; }
-
 // The compact-query instantiations and their entry points are compiled in a translation unit of
 // their own (attention_compact_q.hip, which includes this file for the kernel templates), so that
 // this unit's code object holds exactly the kernels it held before, at the same addresses: moving a
@@ -765,104 +762,77 @@ static float scale_log2(float scale) { return scale * 1.4426950408889634f; }
 // changes output bits.
 #ifndef DL_ATTN_COMPACT_Q_UNIT
 
-// head_dim 64 with 16-byte aligned rows
-static bool hd64_ok(int D, long ld, long ldo) { return D == HD && ld % 8 == 0 && ldo % 8 == 0; }
+// This unit's kernels take the fused QKV buffer (no compact queries) at head_dim 64 with 16-byte
+// aligned rows, and S % 64 == 0 or the packed layout (the callers validate what seqinfo holds:
+// csrc/bindings.cpp)
+static bool hd64_ok(const DlAttn& a) {
+  if (a.q || a.D != HD || a.ld % 8 != 0 || a.ldo % 8 != 0) return false;
+  if (!a.seqinfo) return a.S % 64 == 0;
+  return a.B >= 1 && a.T % 64 == 0 && a.max_slot >= 64 && a.max_slot % 64 == 0 && a.max_slot <= a.T;
+}
 
-int dl_attn_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo, float* lse,
-                int B, int H, int S, int D, float scale, hipStream_t st) {
-  if (D == 128) return dl_attn_hd128_fwd(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, scale, st);
-  if (!hd64_ok(D, ld, ldo) || S % 64 != 0) return -1;
-  dim3 grid((S + 255) / 256, H, B);
-  attn_fwd_kernel<false><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, scale_log2(scale),
-                                               kAttnXcd);
+// All launch sites of one layout.  The kernels are emitted in the order of their first launch
+// site, which is part of what the comment above protects: the fixed-S three (forward, dQ, dK/dV),
+// then the packed three, as the entry points below instantiate this.  The packed kernels read no
+// mbias, take seqinfo in kvinfo's place and T in S's, and the largest slot sizes their grids.
+template <bool PACKED>
+static int hd64_launch(const DlAttn& a, bool bwd, hipStream_t st) {
+  if (!hd64_ok(a)) return -1;
+  const float* mbias = PACKED ? nullptr : a.mbias;
+  const int* info = PACKED ? a.seqinfo : a.kvinfo;
+  const int S = PACKED ? a.T : a.S, rows = PACKED ? a.max_slot : a.S;
+  const float sl2 = a.scale_log2();
+  dim3 grid((rows + 255) / 256, a.H, a.B), grid_kv((rows + 127) / 128, a.H, a.B);
+  if (!bwd) {
+    attn_fwd_kernel<PACKED><<<grid, 256, 0, st>>>(a.kv, a.ld, mbias, info, a.out, a.ldo, a.lse, a.B, a.H, S, sl2,
+                                                  kAttnXcd);
+    return 0;
+  }
+  attn_bwd_dq_kernel<PACKED><<<grid, 256, 0, st>>>(a.kv, a.ld, mbias, info, a.out, a.dout, a.ldo, a.lse, a.delta,
+                                                   a.dqkv, a.dbias, a.B, a.H, S, sl2, a.scale, kAttnXcd);
+  attn_bwd_dkdv_kernel<PACKED><<<grid_kv, 256, 0, st>>>(a.kv, a.ld, mbias, info, a.dout, a.ldo, a.lse, a.delta, a.dqkv,
+                                                        a.B, a.H, S, sl2, a.scale, kAttnXcd);
   return 0;
 }
 
-int dl_attn_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, const bf16_t* out,
-                const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int H,
-                int S, int D, float scale, hipStream_t st) {
-  if (D == 128)
-    return dl_attn_hd128_bwd(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, H, S, scale, st);
-  if (!hd64_ok(D, ld, ldo) || S % 64 != 0) return -1;
-  const float sl2 = scale_log2(scale);
-  dim3 grid_dq((S + 255) / 256, H, B);
-  attn_bwd_dq_kernel<false><<<grid_dq, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B,
-                                                     H, S, sl2, scale, kAttnXcd);
-  dim3 grid_kv((S + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<false><<<grid_kv, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H, S,
-                                                       sl2, scale, kAttnXcd);
-  return 0;
+int dl_attn_hd64_fwd(const DlAttn& a, hipStream_t st) {
+  return !a.seqinfo ? hd64_launch<false>(a, false, st) : hd64_launch<true>(a, false, st);
 }
 
-// Packed (variable-length) batches: seqinfo = int32[2B + 1] (row offsets, then key lengths), lse /
-// delta [H, T]; max_slot (the largest slot, host side) sizes the grids.  The callers validate the
-// layout contract (csrc/bindings.cpp).
-static bool packed_ok(const int* seqinfo, int B, int T, int max_slot) {
-  return seqinfo && B >= 1 && T % 64 == 0 && max_slot >= 64 && max_slot % 64 == 0 && max_slot <= T;
-}
-
-int dl_attn_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B, int T,
-                       int max_slot, int H, int D, float scale, hipStream_t st) {
-  if (!packed_ok(seqinfo, B, T, max_slot)) return -1;
-  if (D == 128) return dl_attn_hd128_varlen_fwd(qkv, ld, seqinfo, out, ldo, lse, B, T, max_slot, H, scale, st);
-  if (!hd64_ok(D, ld, ldo)) return -1;
-  dim3 grid((max_slot + 255) / 256, H, B);
-  attn_fwd_kernel<true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, ldo, lse, B, H, T, scale_log2(scale),
-                                              kAttnXcd);
-  return 0;
-}
-
-int dl_attn_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout, long ldo,
-                       const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T, int max_slot, int H,
-                       int D, float scale, hipStream_t st) {
-  if (!packed_ok(seqinfo, B, T, max_slot)) return -1;
-  if (D == 128)
-    return dl_attn_hd128_varlen_bwd(qkv, ld, seqinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, T, max_slot, H, scale,
-                                    st);
-  if (!hd64_ok(D, ld, ldo)) return -1;
-  const float sl2 = scale_log2(scale);
-  dim3 grid_dq((max_slot + 255) / 256, H, B);
-  attn_bwd_dq_kernel<true><<<grid_dq, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, dout, ldo, lse, delta, dqkv, dbias,
-                                                    B, H, T, sl2, scale, kAttnXcd);
-  dim3 grid_kv((max_slot + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<true><<<grid_kv, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv, B, H, T,
-                                                      sl2, scale, kAttnXcd);
-  return 0;
+int dl_attn_hd64_bwd(const DlAttn& a, hipStream_t st) {
+  return !a.seqinfo ? hd64_launch<false>(a, true, st) : hd64_launch<true>(a, true, st);
 }
 
 #else  // DL_ATTN_COMPACT_Q_UNIT
 
-// Compact queries (struct CompactQ above): q / out / dout / dq [B*Sq, H*64], qcnt int32[B], lse /
-// delta [B, H, Sq]; kv points at K's first column of the [B*S, ld] key / value buffer (V follows H*64
-// columns later); dkv [B*S, 2*H*64].  Head_dim 64 and the fixed-S layout only.
-static bool compact_q_ok(const void* q, const void* kv, const int* qcnt, int B, int H, int S, int Sq, int D, long ld,
-                         long ldo) {
-  return q && kv && qcnt && B >= 1 && H >= 1 && D == HD && S % 64 == 0 && Sq % 64 == 0 && Sq >= 64 && Sq <= S &&
-         ld % 8 == 0 && ld >= 2L * H * HD && ldo % 8 == 0 && ldo >= (long)H * HD;
+// Compact queries (struct CompactQ above, DlAttn's compact block): head_dim 64 and the fixed-S
+// layout only; q / out rows of H*64 columns and key / value rows of 2*H*64, all 16-byte aligned
+static bool hd64q_ok(const DlAttn& a) {
+  return a.q && a.kv && a.qcnt && !a.seqinfo && a.B >= 1 && a.H >= 1 && a.D == HD && a.S % 64 == 0 &&
+         a.Sq % 64 == 0 && a.Sq >= 64 && a.Sq <= a.S && a.ld % 8 == 0 && a.ld >= 2L * a.H * HD && a.ldo % 8 == 0 &&
+         a.ldo >= (long)a.H * HD;
 }
 
-int dl_attn_fwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
-                  bf16_t* out, long ldo, float* lse, int B, int H, int S, int Sq, int D, float scale, hipStream_t st) {
-  if (!compact_q_ok(q, kv, qcnt, B, H, S, Sq, D, ld, ldo)) return -1;
-  const CompactQ cq{q, nullptr, nullptr, 0, qcnt, Sq};
-  dim3 grid((Sq + 255) / 256, H, B);
-  attn_fwd_kernel<false, CompactQ><<<grid, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, ldo, lse, B, H, S,
-                                                         scale_log2(scale), kAttnXcd, cq);
+int dl_attn_hd64q_fwd(const DlAttn& a, hipStream_t st) {
+  if (!hd64q_ok(a)) return -1;
+  const CompactQ cq{a.q, nullptr, nullptr, 0, a.qcnt, a.Sq};
+  dim3 grid((a.Sq + 255) / 256, a.H, a.B);
+  attn_fwd_kernel<false, CompactQ><<<grid, 256, 0, st>>>(a.kv, a.ld, a.mbias, a.kvinfo, a.out, a.ldo, a.lse, a.B, a.H,
+                                                         a.S, a.scale_log2(), kAttnXcd, cq);
   return 0;
 }
 
-int dl_attn_bwd_q(const bf16_t* q, const bf16_t* kv, long ld, const float* mbias, const int* kvinfo, const int* qcnt,
-                  const bf16_t* out, const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dq,
-                  bf16_t* dkv, float* dbias, int B, int H, int S, int Sq, int D, float scale, hipStream_t st) {
-  if (!compact_q_ok(q, kv, qcnt, B, H, S, Sq, D, ld, ldo) || !dq || !dkv) return -1;
-  const float sl2 = scale_log2(scale);
-  const CompactQ cq{q, dq, dkv, 2L * H * HD, qcnt, Sq};
-  dim3 grid_dq((Sq + 255) / 256, H, B);
-  attn_bwd_dq_kernel<false, CompactQ><<<grid_dq, 256, 0, st>>>(kv, ld, mbias, kvinfo, out, dout, ldo, lse, delta,
-                                                               nullptr, dbias, B, H, S, sl2, scale, kAttnXcd, cq);
-  dim3 grid_kv((S + 127) / 128, H, B);
-  attn_bwd_dkdv_kernel<false, CompactQ><<<grid_kv, 256, 0, st>>>(kv, ld, mbias, kvinfo, dout, ldo, lse, delta, nullptr,
-                                                                 B, H, S, sl2, scale, kAttnXcd, cq);
+int dl_attn_hd64q_bwd(const DlAttn& a, hipStream_t st) {
+  if (!hd64q_ok(a) || !a.dq || !a.dkv) return -1;
+  const float sl2 = a.scale_log2();
+  const CompactQ cq{a.q, a.dq, a.dkv, 2L * a.H * HD, a.qcnt, a.Sq};
+  dim3 grid_dq((a.Sq + 255) / 256, a.H, a.B), grid_kv((a.S + 127) / 128, a.H, a.B);
+  attn_bwd_dq_kernel<false, CompactQ><<<grid_dq, 256, 0, st>>>(a.kv, a.ld, a.mbias, a.kvinfo, a.out, a.dout, a.ldo,
+                                                               a.lse, a.delta, nullptr, a.dbias, a.B, a.H, a.S, sl2,
+                                                               a.scale, kAttnXcd, cq);
+  attn_bwd_dkdv_kernel<false, CompactQ><<<grid_kv, 256, 0, st>>>(a.kv, a.ld, a.mbias, a.kvinfo, a.dout, a.ldo, a.lse,
+                                                                 a.delta, nullptr, a.B, a.H, a.S, sl2, a.scale,
+                                                                 kAttnXcd, cq);
   return 0;
 }
 

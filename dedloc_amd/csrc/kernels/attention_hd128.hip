@@ -1,6 +1,6 @@
 // Flash-style self-attention for head_dim 128 (albert-xlarge-v2: 16 heads of 128): the same
 // contract, layouts, masking and MFMA operand arrangement as the head_dim-64 kernels in
-// attention.hip (see its header), reached through dl_attn_fwd / dl_attn_bwd with D == 128.
+// attention.hip (see its header), reached through dl_attn_hd128_fwd / _bwd at the end of this file.
 //
 // A 64-row x 128-dim block of K, V, Q or dO is held in LDS as TWO of the swizzled 64x64 tiles of
 // dl_attn_tile.h (dims 0-63, dims 64-127), so the row reads, the transposed reads and the LDS-DMA
@@ -538,47 +538,42 @@ constexpr int kAttnXcd = 1;
 
 }  // namespace
 
-int dl_attn_hd128_fwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, bf16_t* out, long ldo,
-                      float* lse, int B, int H, int S, float scale, hipStream_t st) {
-  if (S % 64 != 0 || ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  dim3 grid((S + QB - 1) / QB, H, B);
-  attn128_fwd_kernel<false><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, ldo, lse, B, H, S, sl2, kAttnXcd);
+// This unit's kernels take the fused QKV buffer (no compact queries) at head_dim 128 with 16-byte
+// aligned rows, and S % 64 == 0 or the packed layout (the callers validate what seqinfo holds:
+// csrc/bindings.cpp)
+static bool hd128_ok(const DlAttn& a) {
+  if (a.q || a.D != HD || a.ld % 8 != 0 || a.ldo % 8 != 0) return false;
+  if (!a.seqinfo) return a.S % 64 == 0;
+  return a.B >= 1 && a.T % 64 == 0 && a.max_slot >= 64 && a.max_slot % 64 == 0 && a.max_slot <= a.T;
+}
+
+// All launch sites of one layout (as hd64_launch in attention.hip, and with its reason for the
+// order: the fixed-S three, then the packed three).  One grid serves all three kernels: query blocks
+// for the forward and dQ, key blocks for dK/dV, all of QB rows.
+template <bool PACKED>
+static int hd128_launch(const DlAttn& a, bool bwd, hipStream_t st) {
+  if (!hd128_ok(a)) return -1;
+  const float* mbias = PACKED ? nullptr : a.mbias;
+  const int* info = PACKED ? a.seqinfo : a.kvinfo;
+  const int S = PACKED ? a.T : a.S, rows = PACKED ? a.max_slot : a.S;
+  const float sl2 = a.scale_log2();
+  dim3 grid((rows + QB - 1) / QB, a.H, a.B);
+  if (!bwd) {
+    attn128_fwd_kernel<PACKED><<<grid, 256, 0, st>>>(a.kv, a.ld, mbias, info, a.out, a.ldo, a.lse, a.B, a.H, S, sl2,
+                                                     kAttnXcd);
+    return 0;
+  }
+  attn128_bwd_dq_kernel<PACKED><<<grid, 256, 0, st>>>(a.kv, a.ld, mbias, info, a.out, a.dout, a.ldo, a.lse, a.delta,
+                                                      a.dqkv, a.dbias, a.B, a.H, S, sl2, a.scale, kAttnXcd);
+  attn128_bwd_dkdv_kernel<KV_NBUF, PACKED><<<grid, 256, 0, st>>>(a.kv, a.ld, mbias, info, a.dout, a.ldo, a.lse,
+                                                                 a.delta, a.dqkv, a.B, a.H, S, sl2, a.scale, kAttnXcd);
   return 0;
 }
 
-int dl_attn_hd128_bwd(const bf16_t* qkv, long ld, const float* mbias, const int* kvinfo, const bf16_t* out,
-                      const bf16_t* dout, long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B,
-                      int H, int S, float scale, hipStream_t st) {
-  if (S % 64 != 0 || ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  dim3 grid((S + QB - 1) / QB, H, B);  // query blocks for dQ, key blocks for dK/dV: both 128 rows
-  attn128_bwd_dq_kernel<false><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, out, dout, ldo, lse, delta, dqkv, dbias, B, H, S,
-                                              sl2, scale, kAttnXcd);
-  attn128_bwd_dkdv_kernel<KV_NBUF><<<grid, 256, 0, st>>>(qkv, ld, mbias, kvinfo, dout, ldo, lse, delta, dqkv, B, H, S, sl2,
-                                                scale, kAttnXcd);
-  return 0;
+int dl_attn_hd128_fwd(const DlAttn& a, hipStream_t st) {
+  return !a.seqinfo ? hd128_launch<false>(a, false, st) : hd128_launch<true>(a, false, st);
 }
 
-// Packed (variable-length) batches (dl_attn_varlen_fwd / _bwd in attention.hip check the layout arguments)
-int dl_attn_hd128_varlen_fwd(const bf16_t* qkv, long ld, const int* seqinfo, bf16_t* out, long ldo, float* lse, int B,
-                             int T, int max_slot, int H, float scale, hipStream_t st) {
-  if (ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  dim3 grid((max_slot + QB - 1) / QB, H, B);
-  attn128_fwd_kernel<true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, ldo, lse, B, H, T, sl2, kAttnXcd);
-  return 0;
-}
-
-int dl_attn_hd128_varlen_bwd(const bf16_t* qkv, long ld, const int* seqinfo, const bf16_t* out, const bf16_t* dout,
-                             long ldo, const float* lse, float* delta, bf16_t* dqkv, float* dbias, int B, int T,
-                             int max_slot, int H, float scale, hipStream_t st) {
-  if (ld % 8 != 0 || ldo % 8 != 0) return -1;
-  const float sl2 = scale * 1.4426950408889634f;
-  dim3 grid((max_slot + QB - 1) / QB, H, B);
-  attn128_bwd_dq_kernel<true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, out, dout, ldo, lse, delta, dqkv, dbias,
-                                                    B, H, T, sl2, scale, kAttnXcd);
-  attn128_bwd_dkdv_kernel<KV_NBUF, true><<<grid, 256, 0, st>>>(qkv, ld, nullptr, seqinfo, dout, ldo, lse, delta, dqkv,
-                                                               B, H, T, sl2, scale, kAttnXcd);
-  return 0;
+int dl_attn_hd128_bwd(const DlAttn& a, hipStream_t st) {
+  return !a.seqinfo ? hd128_launch<false>(a, true, st) : hd128_launch<true>(a, true, st);
 }

@@ -136,10 +136,8 @@ def _layer_prefix(g: int, i: int) -> str:
     return f"albert.encoder.albert_layer_groups.{g}.albert_layers.{i}."
 
 
-# The residual sums ride in the output-projection / FFN-down GEMM epilogues (C = h, beta = 1): the
-# LayerNorms then read one tensor and write one — 2 of 4 LN HBM passes removed (round 2).
-# (Module constants, not environment knobs: tests and bench/ab_step.py flip them in-process.)
-_RESIDUAL_IN_GEMM = True
+# Schedule switches (module constants, not environment knobs: the tests flip all three in-process,
+# bench/ab_step.py the first two).
 # The backward's data-gradient GEMMs (dX = dY W) run against transposed weight copies made once per
 # encoder call (the 24 layers share them): gemm8 with both operands K-inner beats the K-outer-B form
 # by 5-10% on these shapes (profiles/gemm8_asm_dma_layouts_T131072.log).
@@ -148,10 +146,6 @@ _DGRAD_WT = True
 # applications and add them into the flat gradient once, at the last backward call
 # (gemm_acc_f32_shared).
 _SHARED_WGRAD = True
-# The FFN-up epilogue stores gelu_new'(h) (bf16) for the backward instead of the pre-activation h:
-# it shares the forward's exp2 / rcp, and the FFN-down data gradient's epilogue becomes one multiply
-# instead of a second sigmoid evaluation per element (gemm_gelu_d / gemm_dmul, gemm8 DL_EPI_GELUD / DL_EPI_DMUL).
-_GELU_GRAD_IN_FWD = True
 # AlbertForPreTraining reads only the MLM target rows and one [CLS] row per sequence of the last
 # layer's output, so its last layer application runs on those rows alone (K and V still on every
 # row): _AlbertLastLayerFn over ops.attn_fwd_q / attn_bwd_q.  Head_dim 64 on rectangular batches;
@@ -173,61 +167,31 @@ class _AlbertLayerFn(torch.autograd.Function):
     def forward(ctx, h, mask, lv, H, S, eps):
         O = ops.OPS
         qkv = O.gemm(h, lv["wqkv"], lv["bqkv32"], None, False, True, 0)
+        scale = 1.0 / math.sqrt(qkv.shape[1] // (3 * H))
         if isinstance(mask, PackedBatch):  # packed variable-length batch: h is [T, hidden], S is unused
-            att, lse = ops.attn_varlen_fwd(qkv, mask, H, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)))
+            att, lse = ops.attn_varlen_fwd(qkv, mask, H, scale)
         else:
             mbias, kvinfo = mask
-            att, lse = ops.attn_fwd(qkv, mbias, H, S, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)), kvinfo)
-        if _RESIDUAL_IN_GEMM:
-            # residual sums ride in the GEMM epilogues (C = h, beta = 1): the LayerNorms then read one
-            # tensor and write one (s is the GEMM output itself) — 2 of 4 LN HBM passes removed
-            s1 = O.gemm(att, lv["wo"], lv["bo32"], h, False, True, 0)
-            h1, _, m1, r1 = O.layernorm_fwd(s1, None, lv["ln1g"], lv["ln1b"], eps)
-            # bias + gelu_new fused in the GEMM epilogue; f = gelu_new'(h) (or h itself)
-            f, g = (O.gemm_gelu_d if _GELU_GRAD_IN_FWD else O.gemm_gelu)(h1, lv["w1"], lv["b132"])
-            s2 = O.gemm(g, lv["w2"], lv["b232"], h1, False, True, 0)
-            out, _, m2, r2 = O.layernorm_fwd(s2, None, lv["ln2g"], lv["ln2b"], eps)
-        else:
-            a = O.gemm(att, lv["wo"], lv["bo32"], None, False, True, 0)
-            h1, s1, m1, r1 = O.layernorm_fwd(a, h, lv["ln1g"], lv["ln1b"], eps)
-            f, g = (O.gemm_gelu_d if _GELU_GRAD_IN_FWD else O.gemm_gelu)(h1, lv["w1"], lv["b132"])
-            f2 = O.gemm(g, lv["w2"], lv["b232"], None, False, True, 0)
-            out, s2, m2, r2 = O.layernorm_fwd(f2, h1, lv["ln2g"], lv["ln2b"], eps)
-        ctx.save_for_backward(h, qkv, att, lse, s1, m1, r1, h1, f, g, s2, m2, r2)
-        ctx.lv, ctx.mask, ctx.H, ctx.S = lv, mask, H, S
-        ctx.gelu_d = _GELU_GRAD_IN_FWD
+            att, lse = ops.attn_fwd(qkv, mbias, H, S, scale, kvinfo)
+        out, saved = _post_attention_fwd(O, att, h, lv, eps)
+        ctx.save_for_backward(h, qkv, att, lse, *saved)
+        ctx.lv, ctx.mask, ctx.H, ctx.S, ctx.scale = lv, mask, H, S, scale
         return out
 
     @staticmethod
     def backward(ctx, dy):
         O = ops.OPS
-        h, qkv, att, lse, s1, m1, r1, h1, f, g, s2, m2, r2 = ctx.saved_tensors
-        lv = ctx.lv
-        dy = dy.contiguous()
-        H = ctx.H
-        # LN backward also accumulates colsum(ds) = the bias grad of the Linear that fed it
-        ds2 = O.layernorm_bwd(dy, s2, lv["ln2g"], m2, r2, lv["gln2g"], lv["gln2b"], True, lv["gb2"])
-        _wgrad(O, ds2, g, lv, "gw2")
-        wt = "w2t" in lv  # transposed weight copies present (see _DGRAD_WT)
-        # dgrad * gelu'(h) + ffn bias grad, one kernel (f holds gelu'(h) itself, or h)
-        dfn = O.gemm_dmul if ctx.gelu_d else O.gemm_dgelu
-        df = dfn(ds2, lv["w2t"], f, lv["gb1"], True) if wt else dfn(ds2, lv["w2"], f, lv["gb1"])
-        _wgrad(O, df, h1, lv, "gw1")
-        dh1 = _dgrad(O, df, lv, "w1", ds2)  # residual branch folded in
-        del df
-        ds1 = O.layernorm_bwd(dh1, s1, lv["ln1g"], m1, r1, lv["gln1g"], lv["gln1b"], True, lv["gbo"])
-        _wgrad(O, ds1, att, lv, "gwo")
-        datt = _dgrad(O, ds1, lv, "wo", None)
+        h, qkv, att, lse, *saved = ctx.saved_tensors
+        lv, H = ctx.lv, ctx.H
+        datt, ds1 = _post_attention_bwd(O, dy.contiguous(), att, saved, lv)
         # the QKV bias gradient rides in the attention backward (query: colsum dQ, value: colsum
         # datt, key: exactly zero — softmax is shift invariant), no separate column-sum pass
         if isinstance(ctx.mask, PackedBatch):
-            dqkv = ops.attn_varlen_bwd(qkv, ctx.mask, att, datt, lse, H, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)),
-                                       lv["gbqkv"])
+            dqkv = ops.attn_varlen_bwd(qkv, ctx.mask, att, datt, lse, H, ctx.scale, lv["gbqkv"])
         else:
-            dqkv = ops.attn_bwd(qkv, ctx.mask[0], att, datt, lse, H, ctx.S, 1.0 / math.sqrt(qkv.shape[1] // (3 * H)),
-                                ctx.mask[1], lv["gbqkv"])
+            dqkv = ops.attn_bwd(qkv, ctx.mask[0], att, datt, lse, H, ctx.S, ctx.scale, ctx.mask[1], lv["gbqkv"])
         _wgrad(O, dqkv, h, lv, "gwqkv")
-        dh = _dgrad(O, dqkv, lv, "wqkv", ds1)
+        dh = _dgrad(O, dqkv, lv, "wqkv", ds1)  # residual branch folded in
         return dh, None, None, None, None, None
 
 
@@ -324,37 +288,22 @@ class _AlbertLastLayerFn(torch.autograd.Function):
         hq = h.index_select(0, sel.rows)
         q = O.gemm(hq, lv["wqkv"][:Hd], lv["bqkv32"][:Hd], None, False, True, 0)
         att, lse = ops.attn_fwd_q(q, kv, sel.qcnt, mbias, H, S, scale, kvinfo)
-        s1 = O.gemm(att, lv["wo"], lv["bo32"], hq, False, True, 0)
-        h1, _, m1, r1 = O.layernorm_fwd(s1, None, lv["ln1g"], lv["ln1b"], eps)
-        f, g = (O.gemm_gelu_d if _GELU_GRAD_IN_FWD else O.gemm_gelu)(h1, lv["w1"], lv["b132"])
-        s2 = O.gemm(g, lv["w2"], lv["b232"], h1, False, True, 0)
-        out, _, m2, r2 = O.layernorm_fwd(s2, None, lv["ln2g"], lv["ln2b"], eps)
-        ctx.save_for_backward(h, hq, q, kv, att, lse, s1, m1, r1, h1, f, g, s2, m2, r2)
+        out, saved = _post_attention_fwd(O, att, hq, lv, eps)
+        ctx.save_for_backward(h, hq, q, kv, att, lse, *saved)
         ctx.lv, ctx.mask, ctx.H, ctx.S, ctx.sel, ctx.scale = lv, mask, H, S, sel, scale
-        ctx.gelu_d = _GELU_GRAD_IN_FWD
         return out
 
     @staticmethod
     def backward(ctx, dy):
         O = ops.OPS
-        h, hq, q, kv, att, lse, s1, m1, r1, h1, f, g, s2, m2, r2 = ctx.saved_tensors
+        h, hq, q, kv, att, lse, *saved = ctx.saved_tensors
         lv, sel = ctx.lv, ctx.sel
         Hd = h.shape[1]
-        dy = dy.contiguous()
         # This layer's reduction lengths (B*Sq, and B*S for K/V only) are not the other layers', so it
-        # stays out of their shared slab series: plain fp32 accumulation into the gradient (it is the
-        # first backward call; the layer before it opens the series).
-        ds2 = O.layernorm_bwd(dy, s2, lv["ln2g"], m2, r2, lv["gln2g"], lv["gln2b"], True, lv["gb2"])
-        O.gemm_acc_f32(ds2, g, lv["gw2"], True, False)
-        wt = "w2t" in lv
-        dfn = O.gemm_dmul if ctx.gelu_d else O.gemm_dgelu
-        df = dfn(ds2, lv["w2t"], f, lv["gb1"], True) if wt else dfn(ds2, lv["w2"], f, lv["gb1"])
-        O.gemm_acc_f32(df, h1, lv["gw1"], True, False)
-        dh1 = _dgrad(O, df, lv, "w1", ds2)
-        del df
-        ds1 = O.layernorm_bwd(dh1, s1, lv["ln1g"], m1, r1, lv["gln1g"], lv["gln1b"], True, lv["gbo"])
-        O.gemm_acc_f32(ds1, att, lv["gwo"], True, False)
-        datt = _dgrad(O, ds1, lv, "wo", None)
+        # stays out of their shared slab series: its views carry no wg_first, and _wgrad accumulates
+        # straight into the fp32 gradient (it is the first backward call; the layer before it opens
+        # the series).
+        datt, ds1 = _post_attention_bwd(O, dy.contiguous(), att, saved, lv)
         dq, dkv, _ = ops.attn_bwd_q(q, kv, sel.qcnt, ctx.mask[0], att, datt, lse, ctx.H, ctx.S, ctx.scale, ctx.mask[1],
                                     lv["gbqkv"])
         O.gemm_acc_f32(dq, hq, lv["gwqkv"][:Hd], True, False)
@@ -375,6 +324,42 @@ class _AlbertLastLayerFn(torch.autograd.Function):
             dh = O.gemm(dkv, lv["wqkv"][Hd:], None, None, False, False, 0)
         dh.index_copy_(0, sel.rows, dhq.index_select(0, sel.owner))
         return dh, None, None, None, None, None, None
+
+
+def _post_attention_fwd(O, att, res, lv, eps):
+    """The half of the layer behind attention, on the rows of ``att``: output projection -> LN ->
+    FFN-up with gelu_new -> FFN-down -> LN.  Both residual sums (``res``, the rows of the layer's
+    input under ``att``, and h1) ride in the GEMM epilogues (C = residual, beta = 1), so each
+    LayerNorm reads one tensor and writes one: 2 of 4 LN HBM passes removed.  The FFN-up epilogue
+    stores f = gelu_new'(h) (bf16) for the backward instead of the pre-activation h: it shares the
+    forward's exp2 / rcp, and the FFN-down data gradient's epilogue becomes one multiply instead of a
+    second sigmoid evaluation per element (gemm_gelu_d / gemm_dmul, gemm8 DL_EPI_GELUD / DL_EPI_DMUL).
+    Returns the layer's output and the tensors ``_post_attention_bwd`` needs."""
+    s1 = O.gemm(att, lv["wo"], lv["bo32"], res, False, True, 0)
+    h1, _, m1, r1 = O.layernorm_fwd(s1, None, lv["ln1g"], lv["ln1b"], eps)
+    f, g = O.gemm_gelu_d(h1, lv["w1"], lv["b132"])
+    s2 = O.gemm(g, lv["w2"], lv["b232"], h1, False, True, 0)
+    out, _, m2, r2 = O.layernorm_fwd(s2, None, lv["ln2g"], lv["ln2b"], eps)
+    return out, (s1, m1, r1, h1, f, g, s2, m2, r2)
+
+
+def _post_attention_bwd(O, dy, att, saved, lv):
+    """Backward of ``_post_attention_fwd``: (datt, ds1), the gradients of ``att`` and of the first
+    residual sum (the caller folds ds1 into its input gradient).  Accumulates the weight and bias
+    gradients of the four parameter groups behind attention."""
+    s1, m1, r1, h1, f, g, s2, m2, r2 = saved
+    # LN backward also accumulates colsum(ds) = the bias grad of the Linear that fed it
+    ds2 = O.layernorm_bwd(dy, s2, lv["ln2g"], m2, r2, lv["gln2g"], lv["gln2b"], True, lv["gb2"])
+    _wgrad(O, ds2, g, lv, "gw2")
+    # dgrad * gelu'(h) + ffn bias grad, one kernel; against the transposed weight copy when the
+    # views carry one (see _DGRAD_WT)
+    df = O.gemm_dmul(ds2, lv["w2t"], f, lv["gb1"], True) if "w2t" in lv else O.gemm_dmul(ds2, lv["w2"], f, lv["gb1"])
+    _wgrad(O, df, h1, lv, "gw1")
+    dh1 = _dgrad(O, df, lv, "w1", ds2)  # residual branch folded in
+    del df
+    ds1 = O.layernorm_bwd(dh1, s1, lv["ln1g"], m1, r1, lv["gln1g"], lv["gln1b"], True, lv["gbo"])
+    _wgrad(O, ds1, att, lv, "gwo")
+    return _dgrad(O, ds1, lv, "wo", None), ds1
 
 
 def _wgrad(O, dy, x, lv, name):
@@ -576,12 +561,11 @@ class AlbertPreTrainedModel(nn.Module):
         return _AlbertLayerFn.apply(h, mask, lv, c.num_attention_heads, S, c.layer_norm_eps)
 
     def last_layer_rows_supported(self) -> bool:
-        """Whether the last layer can run on compact rows (LastLayerRows): the module switch, the
-        residual-in-GEMM layer form the compact layer is written in, one layer per group application
-        and head_dim 64 (the only head size with compact-query attention kernels)."""
+        """Whether the last layer can run on compact rows (LastLayerRows): the module switch, one
+        layer per group application and head_dim 64 (the only head size with compact-query attention
+        kernels)."""
         c = self.config
-        return (_LAST_LAYER_ROWS and _RESIDUAL_IN_GEMM and c.inner_group_num == 1
-                and c.hidden_size == 64 * c.num_attention_heads)
+        return _LAST_LAYER_ROWS and c.inner_group_num == 1 and c.hidden_size == 64 * c.num_attention_heads
 
     def _packed(self, pack_sequences, input_ids, attention_mask, token_type_ids, lengths, labels=None):
         """The PackedBatch of this call, or None when the call runs on the rectangular layout."""
@@ -662,21 +646,21 @@ class AlbertPreTrainedModel(nn.Module):
             views = [[_with_transposed_weights(lv) for lv in row] for row in views]
         per_group = c.num_hidden_layers // c.num_hidden_groups
         group_of = [int(layer / per_group) for layer in range(c.num_hidden_layers)]
+        pruned = c.num_hidden_layers - 1 if last_rows is not None else None
+        # The applications of each group's weights that share one slab series.  The compact layer
+        # accumulates its weight gradients directly, outside the series: the application before it
+        # opens the series.
+        uses = [[layer for layer in range(c.num_hidden_layers) if group_of[layer] == g and layer != pruned]
+                for g in range(c.num_hidden_groups)]
         for layer in range(c.num_hidden_layers):
             g = group_of[layer]
-            uses = [x for x in range(c.num_hidden_layers) if group_of[x] == g]
             for i in range(c.inner_group_num):
                 lv = views[g][i]
-                pruned = last_rows is not None and layer == c.num_hidden_layers - 1
-                if last_rows is not None and uses[-1] == c.num_hidden_layers - 1:
-                    # the compact layer accumulates its weight gradients directly, outside the slab
-                    # series: the application before it opens the series
-                    uses = uses[:-1]
-                if not pruned and _SHARED_WGRAD and torch.is_grad_enabled():
+                if layer != pruned and _SHARED_WGRAD and torch.is_grad_enabled():
                     # backward runs the layers in reverse: the last application is the first to
                     # write the weight's gradient slabs, the first application sums them in
-                    lv = dict(lv, wg_first=layer == uses[-1], wg_last=layer == uses[0])
-                h = self._albert_layer(h, lv, mask, Sp, last_rows if pruned else None)
+                    lv = dict(lv, wg_first=layer == uses[g][-1], wg_last=layer == uses[g][0])
+                h = self._albert_layer(h, lv, mask, Sp, last_rows if layer == pruned else None)
         return h
 
     def num_parameters(self) -> int:
