@@ -1,0 +1,95 @@
+"""The MLM head's decoder + loss alone, forward and backward: the fused kernels
+(ops.mlm_cross_entropy) against the composed path (ops.linear then ops.cross_entropy) on the same
+inputs, at the headline micro-batch's M = 39424 target rows and V = 30000.
+
+    python bench/mlm_head_bench.py [--M 39424] [--V 30000] [--rounds 3] [--iters 10] [--out FILE]
+
+The arms alternate call by call inside each round (device events around one forward + backward,
+cold MALL, median of --iters after a warm-up of every arm); one JSON line per round with the time
+per call and ``max_memory_allocated`` of each arm above the bytes held before it ran, appended to
+--out (default profiles/mlm_xent.jsonl)."""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--M", type=int, default=39424)
+    ap.add_argument("--V", type=int, default=30000)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlm_xent.jsonl"))
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("mlm_head_bench needs a GPU")
+    import dedloc_amd.ops as ops
+
+    M, V = args.M, args.V
+    g = torch.Generator().manual_seed(0)
+    t = torch.randn(M, 128, generator=g).bfloat16().cuda().requires_grad_()
+    w = (torch.randn(V, 128, generator=g) * 0.5).bfloat16().cuda()
+    bias = (torch.randn(V, generator=g) * 0.1).bfloat16().cuda()
+    labels = torch.randint(0, V, (M,), generator=g).cuda()
+    gw = torch.zeros(V, 128, device="cuda")
+    gb = torch.zeros(V, device="cuda")
+    flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")  # evicts the 256 MB MALL
+
+    def fused():
+        return ops.mlm_cross_entropy(t, w, bias, labels, gw, gb)
+
+    def composed():
+        return ops.cross_entropy(ops.linear(t, w, bias, gw, gb), labels)
+
+    arms = {"fused": fused, "composed": composed}
+
+    def call(fn):
+        t.grad = None
+        loss = fn()
+        loss.backward()
+        return loss
+
+    peak = {}
+    for name, fn in arms.items():  # warm-up of both arms, and each arm's peak memory on its own
+        call(fn)
+        torch.cuda.synchronize()
+        base = torch.cuda.memory_allocated()
+        torch.cuda.reset_peak_memory_stats()
+        loss = call(fn)
+        torch.cuda.synchronize()
+        peak[name] = torch.cuda.max_memory_allocated() - base
+        peak[name + "_loss"] = float(loss)
+        del loss
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    for rnd in range(args.rounds):
+        evs = {name: [] for name in arms}
+        for _ in range(args.iters):
+            for name, fn in arms.items():
+                flush.zero_()
+                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                a.record()
+                call(fn)
+                b.record()
+                evs[name].append((a, b))
+        torch.cuda.synchronize()
+        rec = {"bench": "mlm_head", "M": M, "V": V, "round": rnd, "iters": args.iters,
+               "logits_bytes": M * V * 2}
+        for name in arms:
+            ts = sorted(a.elapsed_time(b) * 1e3 for a, b in evs[name])
+            rec[name + "_us"] = round(ts[len(ts) // 2], 1)
+            rec[name + "_peak_bytes"] = peak[name]
+            rec[name + "_loss"] = peak[name + "_loss"]
+        rec["peak_drop_bytes"] = peak["composed"] - peak["fused"]
+        print(json.dumps(rec), flush=True)
+        with open(args.out, "a") as f:
+            f.write(json.dumps(rec) + "\n")
+
+
+if __name__ == "__main__":
+    main()

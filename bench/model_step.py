@@ -53,8 +53,14 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--attn", default="fused", choices=["fused", "composed"],
                     help="composed: head_dim 128 (albert-xlarge-v2) takes ops.attn_composed_* instead of the flash kernels")
+    ap.add_argument("--mlm_loss", default="fused", choices=["fused", "composed"],
+                    help="composed: the decoder GEMM and ops.cross_entropy instead of ops.mlm_cross_entropy")
     args = ap.parse_args()
     dev = torch.device("cuda")
+    if args.mlm_loss == "composed":
+        import dedloc_amd.models.albert as albert
+
+        albert._FUSED_MLM_LOSS = False
     if args.attn == "composed":
         import dedloc_amd.ops as ops
 
@@ -143,7 +149,7 @@ def main():
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.iters
     fl = flops_per_sample(cfg, args.seq, P) * args.batch  # counted on full rows, whatever the lengths
-    print(json.dumps({"impl": args.impl, "config": args.config, "attn": args.attn, "batch": args.batch, "seq": args.seq, "ms_per_microstep": dt * 1e3,
+    print(json.dumps({"impl": args.impl, "config": args.config, "attn": args.attn, "mlm_loss": args.mlm_loss, "batch": args.batch, "seq": args.seq, "ms_per_microstep": dt * 1e3,
                       "samples_per_s": args.batch / dt, "tflops": fl / dt / 1e12, "loss": float(loss.detach()),
                       "length_mode": args.length_mode, "pack_sequences": bool(args.pack_sequences), **shares}), flush=True)
 

@@ -426,6 +426,67 @@ std::tuple<at::Tensor, at::Tensor> xent_eval(const at::Tensor& logits, const at:
   return {row_loss, row_rank};
 }
 
+// ------------------------------------------------------------------ fused MLM head (mlm_xent.hip)
+// The operands both directions share: t [M, 128] and w [V, 128] bf16 with unit column stride, bias
+// [V] bf16 or fp32, labels int64 [M]; the bias scratch comes from the caching allocator.
+inline DlMlmXent mlm_xent_desc(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias,
+                               const at::Tensor& labels, int64_t ignore_index, at::Tensor& bias_ws, const char* what) {
+  for (const at::Tensor* x : {&t, &w})
+    TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 && x->dim() == 2 && x->stride(1) == 1, what,
+                ": t and w must be 2-D bf16 GPU tensors with unit column stride");
+  TORCH_CHECK(t.size(1) == w.size(1), what, ": t [M, E] and w [V, E]");
+  expect(labels, at::kLong, "labels");
+  TORCH_CHECK(bias.is_cuda() && bias.is_contiguous() && bias.numel() == w.size(0) &&
+                  (bias.scalar_type() == at::kBFloat16 || bias.scalar_type() == at::kFloat),
+              what, ": bias must be a contiguous bf16 or fp32 GPU tensor of V values");
+  TORCH_CHECK(labels.numel() == t.size(0), what, ": labels has ", labels.numel(), " elements for ", t.size(0), " rows");
+  TORCH_CHECK(t.size(0) <= INT32_MAX - 256 && w.size(0) >= 1 && w.size(0) <= INT32_MAX - 64, what, ": M or V out of range");
+  DlMlmXent a;
+  a.t = cbf(t), a.ldt = t.stride(0);
+  a.w = cbf(w), a.ldw = w.stride(0);
+  a.bias = bias.data_ptr(), a.bias_bf16 = bias.scalar_type() == at::kBFloat16;
+  a.labels = labels.data_ptr<long>(), a.ignore_index = (int)ignore_index;
+  a.M = (int)t.size(0), a.V = (int)w.size(0), a.E = (int)t.size(1);
+  bias_ws = at::empty({(a.V + 63) / 64 * 64}, t.options().dtype(at::kFloat));
+  a.bias_ws = f32(bias_ws);
+  return a;
+}
+
+std::tuple<at::Tensor, at::Tensor> mlm_xent_fwd(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias,
+                                                const at::Tensor& labels, int64_t ignore_index) {
+  at::Tensor bias_ws;
+  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, bias_ws, "mlm_xent_fwd");
+  auto lse = at::empty({a.M}, t.options().dtype(at::kFloat));
+  auto loss = at::empty({}, lse.options());
+  auto row_loss = at::empty({a.M}, lse.options());
+  a.lse = f32(lse), a.loss = f32(loss), a.row_loss = f32(row_loss);
+  check(dl_mlm_xent_fwd(a, cur_stream(t)), "mlm_xent_fwd");
+  return {loss, lse};
+}
+
+at::Tensor mlm_xent_bwd(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias, const at::Tensor& labels,
+                        const at::Tensor& lse, const at::Tensor& gloss, const c10::optional<at::Tensor>& gw,
+                        const c10::optional<at::Tensor>& gb, int64_t ignore_index) {
+  at::Tensor bias_ws;
+  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, bias_ws, "mlm_xent_bwd");
+  expect(lse, at::kFloat, "lse");
+  expect(gloss, at::kFloat, "gloss");
+  TORCH_CHECK(lse.numel() == a.M && gloss.numel() == 1, "mlm_xent_bwd: lse [M] and a scalar gloss");
+  TORCH_CHECK(gw.has_value() == gb.has_value(), "mlm_xent_bwd: gw and gb come together");
+  if (gw.has_value()) {
+    expect(*gw, at::kFloat, "gw");
+    expect(*gb, at::kFloat, "gb");
+    TORCH_CHECK(gw->numel() == (int64_t)a.V * a.E && gb->numel() == a.V, "mlm_xent_bwd: gw [V, E] and gb [V]");
+    a.gw = f32(*gw), a.gb = f32(*gb);
+  }
+  auto dt = at::empty({a.M, a.E}, t.options());
+  auto row_ws = at::empty({3 * (((int64_t)a.M + 63) / 64 * 64)}, t.options().dtype(at::kFloat));
+  a.lse = f32(lse), a.gloss = f32(gloss), a.row_ws = f32(row_ws);
+  a.dt = bf(dt), a.lddt = a.E;
+  check(dl_mlm_xent_bwd(a, cur_stream(t)), "mlm_xent_bwd");
+  return dt;
+}
+
 // ------------------------------------------------------------------ kNN evaluation (knn.hip)
 // Everything outside the kernels' domain raises here, before a launch.
 std::tuple<at::Tensor, at::Tensor> knn_topk(const at::Tensor& q, const at::Tensor& bank, int64_t k, int64_t splits) {
@@ -1985,6 +2046,8 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("embed_bwd", &embed_bwd);
   m.impl("xent_fwd_bwd", &xent_fwd_bwd);
   m.impl("xent_eval", &xent_eval);
+  m.impl("mlm_xent_fwd", &mlm_xent_fwd);
+  m.impl("mlm_xent_bwd", &mlm_xent_bwd);
   m.impl("knn_topk", &knn_topk);
   m.impl("knn_vote", &knn_vote);
   m.impl("attn_fwd", &attn_fwd);

@@ -196,6 +196,26 @@ int dl_attn_hd64q_bwd(const DlAttn& a, hipStream_t st);
 int dl_attn_hd128_fwd(const DlAttn& a, hipStream_t st);
 int dl_attn_hd128_bwd(const DlAttn& a, hipStream_t st);
 
+// One fused MLM-head call (mlm_xent.hip): logits = t W^T + bias and the mean cross-entropy over the
+// rows whose label is not ignore_index, forward or backward, without the [M, V] logits in memory.
+struct DlMlmXent {
+  const bf16_t* t = nullptr; long ldt = 0;  // [M, E] the head's LayerNorm output
+  const bf16_t* w = nullptr; long ldw = 0;  // [V, E] the tied word embeddings
+  const void* bias = nullptr; int bias_bf16 = 0;  // [V], bf16 or fp32
+  const long* labels = nullptr; int ignore_index = -100;  // [M]
+  int M = 0, V = 0, E = 0;  // E must be 128; rows of t, w, dt 16-byte aligned
+  float* bias_ws = nullptr;  // scratch: V rounded up to 64 floats
+  float* lse = nullptr;      // [M] log2 units: written by the forward, read by the backward
+  // forward: per-row loss [M] (scratch) and the mean over the live rows (0 without one)
+  float* row_loss = nullptr; float* loss = nullptr;
+  // backward: gloss = d/d loss (device scalar); row_ws scratch of 3 * (M rounded up to 64) floats;
+  // dt [M, E] bf16; gw [V, E] / gb [V] fp32, dense, ADDED into (both or neither)
+  const float* gloss = nullptr; float* row_ws = nullptr;
+  bf16_t* dt = nullptr; long lddt = 0; float* gw = nullptr; float* gb = nullptr;
+};
+int dl_mlm_xent_fwd(const DlMlmXent& a, hipStream_t st);
+int dl_mlm_xent_bwd(const DlMlmXent& a, hipStream_t st);
+
 // swav.hip
 int dl_sinkhorn_ws(int n, int K);
 int dl_sinkhorn(const float* scores, float* Q, float* ws, int n, int K, int bs, float eps, int iters,

@@ -1,0 +1,449 @@
+// Fused MLM head: the tied decoder GEMM logits = t W^T + bias and the token cross-entropy over
+// them, forward and backward, without the [M, V] logits (or their gradient) ever reaching memory.
+//
+//   t [M, 128] bf16   the head's LayerNorm output          labels int64 [M] (ignore_index: dead row)
+//   w [V, 128] bf16   the word embeddings (tied decoder)   bias [V] bf16 or fp32
+//
+// It is the head_dim-128 flash attention (attention_hd128.hip) with "keys = vocabulary rows": one
+// operand's fragments stay in registers, 64-row blocks of the other stream through a two-slot
+// LDS-DMA ring as the two swizzled 64x64 tiles of dl_attn_tile.h, scores come out of
+// v_mfma_f32_32x32x16_bf16 with one row of the register operand per lane, and the softmax runs in
+// log2 units.  Three kernels, split as the attention forward, dQ and dK/dV are:
+//
+//   fwd    token on the lane.  A wave holds TWO 32-token sub-blocks of t (64 VGPRs): there is no
+//          output accumulator, and every w fragment read from LDS then feeds two MFMAs.  Running
+//          max / sum per lane, halves combined by v_permlane32_swap, the target logit picked up in
+//          the tile that holds the label.  Writes lse (log2 units) and the per-row loss.
+//   bwd dt token on the lane, one sub-block per wave: t 32 + dt 64 + scores 32 registers.
+//          P = exp2(s + bias - lse) is recomputed, dS = (P - onehot) g / count is packed to bf16
+//          and dt += dS W accumulates from transposed reads of the same w tiles.
+//   bwd dw vocabulary on the lane.  A workgroup owns 64 vocabulary rows: waves 0/1 and 2/3 hold the
+//          two 32-row sub-blocks of w, and of every streamed 64-token block waves 0-1 take the
+//          first 32 tokens, waves 2-3 the other 32.  dW^T += t^T dS (64 registers) and dbias from
+//          the same dS; the two token halves meet in LDS in a fixed order, then the owning wave
+//          ADDS into the fp32 gradient rows with plain loads and stores (no atomics).
+//
+// Tails.  The bias goes through a small preparation kernel into fp32 log2 units, padded to whole
+// tiles with -1e30: a vocabulary row past V - 1 is loaded as row V - 1 and its score is masked by
+// its bias.  Token rows past M - 1 are loaded as row M - 1, stored nowhere and counted nowhere
+// (scale 0, lse +1e30 in the backward's per-row table).
+// The mean is taken by one block in a fixed order: no float atomics anywhere in this file.
+#include "dl_attn_tile.h"
+#include "dl_common.h"
+#include "dl_kernels.h"
+
+namespace {
+
+constexpr int E = 128;  // embedding size: a 64-row block is two 64x64 tiles
+constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+constexpr int NBUF = 2;                           // ring slots
+constexpr int W_STAGE = 2 * TILE_BYTES + 256;     // fwd, dt: [w dims 0-63 | w dims 64-127 | 64 bias]
+constexpr int T_STAGE = 2 * TILE_BYTES + 768;     // dw: [t dims 0-63 | t dims 64-127 | lse | scale | label]
+constexpr int FWD_ROWS = 256, DT_ROWS = 128, DW_ROWS = 64;  // rows a workgroup owns
+
+// dma_tile with the source row clamped to n - 1 (the last tile of a tail re-reads the last row)
+__device__ __forceinline__ void dma_tile_clamp(const bf16_t* g, long ld, int row0, int n, uint8_t* tile, int w,
+                                               int lane) {
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int p = w + 4 * j;
+    const int row = 8 * p + (lane >> 3);
+    const int c = (lane & 7) ^ swzf((row >> 1) & 7);
+    dma16(g + (long)min(row0 + row, n - 1) * ld + c * 8, lds_u32(tile + p * 1024));
+  }
+}
+// the two 64x64 tiles of the 64-row x 128-column block starting at row row0 of an n-row matrix
+__device__ __forceinline__ void dma_block(const bf16_t* g, long ld, int row0, int n, uint8_t* tiles, int w, int lane) {
+  if (row0 + 64 <= n) {
+    dma_tile(g, ld, row0, tiles, w, lane);
+    dma_tile(g + 64, ld, row0, tiles + TILE_BYTES, w, lane);
+  } else {
+    dma_tile_clamp(g, ld, row0, n, tiles, w, lane);
+    dma_tile_clamp(g + 64, ld, row0, n, tiles + TILE_BYTES, w, lane);
+  }
+}
+// row fragment ks (0..7) of a block: columns 16 ks + 8 hh .. +7 of row `row`
+__device__ __forceinline__ bf16x8 block_row_frag(const uint8_t* tiles, int row, int ks, int hh) {
+  return lds_row_frag(tiles + (ks >> 2) * TILE_BYTES, row, 2 * (ks & 3) + hh);
+}
+// transposed operand for column block t (0..3: columns 32 t .. 32 t + 31)
+__device__ __forceinline__ bf16x8 block_tr(const uint8_t* tiles, int kbase, int hh, int t, int lane) {
+  return tr_operand(tiles + (t >> 1) * TILE_BYTES, kbase, hh, t & 1, lane);
+}
+// this lane's fragments of row `row`: columns 16 ks + 8 hh .. +7
+__device__ __forceinline__ void load_row_frags(const bf16_t* g, long ld, int row, int hh, bf16x8 (&f)[8]) {
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) f[ks] = gload8(g + (long)row * ld + ks * 16 + 8 * hh);
+}
+__device__ __forceinline__ float max16(const floatx16& x) {
+  float v = vmax3(x[0], x[1], x[2]);
+  v = vmax3(v, x[3], x[4]);
+  v = vmax3(v, x[5], x[6]);
+  v = vmax3(v, x[7], x[8]);
+  v = vmax3(v, x[9], x[10]);
+  v = vmax3(v, x[11], x[12]);
+  v = vmax3(v, x[13], x[14]);
+  return vmax3(v, x[15], x[15]);
+}
+__device__ __forceinline__ void zero(floatx16& x) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) x[i] = 0.f;
+}
+__device__ __forceinline__ void ring_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// ---------------------------------------------------------------------------------- preparation
+// out[i] = bias[i] * log2(e) for i < V, -1e30 up to the next multiple of 64
+__global__ void mlm_bias_kernel(const void* __restrict__ bias, int bias_bf16, float* __restrict__ out, int V, int Vp) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= Vp) return;
+  float b = NEG_BIG;
+  if (i < V) b = (bias_bf16 ? bf2f(static_cast<const bf16_t*>(bias)[i]) : static_cast<const float*>(bias)[i]) * LOG2E;
+  out[i] = b;
+}
+
+__device__ __forceinline__ float live_rows(const long* __restrict__ labels, int M, int ignore_index, float* scratch) {
+  float c = 0.f;
+  for (int i = threadIdx.x; i < M; i += blockDim.x) c += labels[i] != ignore_index ? 1.f : 0.f;
+  return block_sum(c, scratch);
+}
+
+// loss = sum of the per-row losses / live rows (0 without a live row), one block, fixed order
+__global__ __launch_bounds__(1024) void mlm_loss_kernel(const float* __restrict__ row_loss,
+                                                         const long* __restrict__ labels, int M, int ignore_index,
+                                                         float* __restrict__ loss) {
+  __shared__ float scratch[16];
+  const float c = live_rows(labels, M, ignore_index, scratch);
+  float s = 0.f;
+  for (int i = threadIdx.x; i < M; i += blockDim.x) s += row_loss[i];
+  s = block_sum(s, scratch);
+  if (threadIdx.x == 0) loss[0] = c > 0.f ? s / c : 0.f;
+}
+
+// The backward's per-row table, three arrays of Mp = M rounded up to 64: lse (+1e30 past M - 1),
+// scale = gloss / live rows on live rows and 0 elsewhere, label as int32 (-1 on dead rows).
+__global__ __launch_bounds__(1024) void mlm_rows_kernel(const float* __restrict__ lse, const long* __restrict__ labels,
+                                                         const float* __restrict__ gloss, int M, int Mp,
+                                                         int ignore_index, float* __restrict__ info) {
+  __shared__ float scratch[16];
+  const float c = live_rows(labels, M, ignore_index, scratch);
+  const float scale = c > 0.f ? gloss[0] / c : 0.f;
+  int* lab = reinterpret_cast<int*>(info + 2 * (long)Mp);
+  for (int i = threadIdx.x; i < Mp; i += blockDim.x) {
+    const bool live = i < M && labels[i] != ignore_index;
+    info[i] = i < M ? lse[i] : -NEG_BIG;
+    info[Mp + i] = live ? scale : 0.f;
+    lab[i] = live ? (int)labels[i] : -1;
+  }
+}
+
+// ------------------------------------------------------------------------------------------ fwd
+__global__ __launch_bounds__(256, 2) void mlm_xent_fwd_kernel(const bf16_t* __restrict__ t, long ldt,
+                                                               const bf16_t* __restrict__ w, long ldw,
+                                                               const float* __restrict__ biasl2,
+                                                               const long* __restrict__ labels, float* __restrict__ lse,
+                                                               float* __restrict__ row_loss, int M, int V,
+                                                               int ignore_index) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * W_STAGE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int nt = (V + 63) / 64;
+  auto issue = [&](int vt) {  // vocabulary tile vt -> slot vt % NBUF
+    uint8_t* slot = smem + (vt % NBUF) * W_STAGE;
+    dma_block(w, ldw, vt * 64, V, slot, wv, lane);
+    dma_f32x64(biasl2 + vt * 64, slot + 2 * TILE_BYTES, lane);
+  };
+  issue(0);
+
+  const int row0 = blockIdx.x * FWD_ROWS + wv * 64 + r;
+  bf16x8 tf[2][8];
+  int lab[2];
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int row = row0 + 32 * u;
+    const int rc = min(row, M - 1);
+    load_row_frags(t, ldt, rc, hh, tf[u]);
+    const long l = labels[rc];
+    lab[u] = (row < M && l != ignore_index) ? (int)l : -1;
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    settle(lab[u]);
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) settle(tf[u][ks]);
+  }
+  float m[2] = {NEG_BIG, NEG_BIG}, l[2] = {0.f, 0.f}, xl[2] = {0.f, 0.f};
+
+  wait_vm_all();
+  for (int vt = 0; vt < nt; ++vt) {
+    // stage vt landed (this wave) -> barrier: every wave's pieces landed and every wave is done
+    // with the other slot, which the stage issued next overwrites
+    ring_wait();
+    __syncthreads();
+    if (vt + 1 < nt) issue(vt + 1);
+    const uint8_t* Ws = smem + (vt % NBUF) * W_STAGE;
+    const float* bs = reinterpret_cast<const float*>(Ws + 2 * TILE_BYTES);
+    floatx16 s[2][2];
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) zero(s[u][j]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) {
+        const bf16x8 a = block_row_frag(Ws, 32 * j + r, ks, hh);
+        s[0][j] = mfma32(a, tf[0][ks], s[0][j]);
+        s[1][j] = mfma32(a, tf[1][ks], s[1][j]);
+      }
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[u][j][i] = fmaf(s[u][j][i], LOG2E, bs[32 * j + crow(i, hh)]);
+      const int d = lab[u] - vt * 64;  // the label's row in this tile
+      if (__ballot((unsigned)d < 64u) != 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (32 * j + crow(i, hh) == d) xl[u] = s[u][j][i];
+      }
+      const float mx = half_max(vmax3(max16(s[u][0]), max16(s[u][1]), m[u]));
+      const float nm = -mx;
+      float rsa[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rsa[i & 3] += __builtin_amdgcn_exp2f(s[u][j][i] + nm);
+      l[u] = fmaf(l[u], __builtin_amdgcn_exp2f(m[u] + nm), half_sum((rsa[0] + rsa[1]) + (rsa[2] + rsa[3])));
+      m[u] = mx;
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const int row = row0 + 32 * u;
+    const float target = half_sum(xl[u]);  // one half found it, the other holds 0
+    const float l2 = m[u] + log2f(l[u]);
+    if (row < M && hh == 0) {
+      lse[row] = l2;
+      row_loss[row] = lab[u] >= 0 ? (l2 - target) * LN2 : 0.f;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ bwd dt
+__global__ __launch_bounds__(256, 2) void mlm_xent_bwd_dt_kernel(const bf16_t* __restrict__ t, long ldt,
+                                                                  const bf16_t* __restrict__ w, long ldw,
+                                                                  const float* __restrict__ biasl2,
+                                                                  const float* __restrict__ info, int Mp,
+                                                                  bf16_t* __restrict__ dt, long lddt, int M, int V) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * W_STAGE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int nt = (V + 63) / 64;
+  auto issue = [&](int vt) {
+    uint8_t* slot = smem + (vt % NBUF) * W_STAGE;
+    dma_block(w, ldw, vt * 64, V, slot, wv, lane);
+    dma_f32x64(biasl2 + vt * 64, slot + 2 * TILE_BYTES, lane);
+  };
+  issue(0);
+
+  const int row = blockIdx.x * DT_ROWS + wv * 32 + r;
+  const int rc = min(row, M - 1);
+  bf16x8 tf[8];
+  load_row_frags(t, ldt, rc, hh, tf);
+  float l2 = info[rc];
+  float gs = row < M ? info[Mp + rc] : 0.f;
+  int lab = row < M ? reinterpret_cast<const int*>(info)[2 * (long)Mp + rc] : -1;
+  settle(l2);
+  settle(gs);
+  settle(lab);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) settle(tf[ks]);
+  floatx16 o[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) zero(o[c]);
+
+  wait_vm_all();
+  for (int vt = 0; vt < nt; ++vt) {
+    ring_wait();
+    __syncthreads();
+    if (vt + 1 < nt) issue(vt + 1);
+    const uint8_t* Ws = smem + (vt % NBUF) * W_STAGE;
+    const float* bs = reinterpret_cast<const float*>(Ws + 2 * TILE_BYTES);
+    floatx16 s[2];
+    zero(s[0]);
+    zero(s[1]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) s[j] = mfma32(block_row_frag(Ws, 32 * j + r, ks, hh), tf[ks], s[j]);
+    const int d = lab - vt * 64;
+    if (__ballot((unsigned)d < 64u) == 0) {  // no label of this wave's rows in the tile: dS = P g / count
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          s[j][i] = __builtin_amdgcn_exp2f(fmaf(s[j][i], LOG2E, bs[32 * j + crow(i, hh)] - l2)) * gs;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float p = __builtin_amdgcn_exp2f(fmaf(s[j][i], LOG2E, bs[32 * j + crow(i, hh)] - l2));
+          s[j][i] = (p - (32 * j + crow(i, hh) == d ? 1.f : 0.f)) * gs;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int ss = 0; ss < 2; ++ss) {
+        const bf16x8 pb = pack_acc(s[j], ss);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[c] = mfma32(block_tr(Ws, 32 * j + 16 * ss, hh, c, lane), pb, o[c]);
+      }
+  }
+  if (row < M) {
+    bf16_t* op = dt + (long)row * lddt;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        store4(op + 32 * c + 8 * v + 4 * hh, o[c][4 * v], o[c][4 * v + 1], o[c][4 * v + 2], o[c][4 * v + 3]);
+  }
+}
+
+// ------------------------------------------------------------------------------------------ bwd dw
+__global__ __launch_bounds__(256, 2) void mlm_xent_bwd_dw_kernel(const bf16_t* __restrict__ t, long ldt,
+                                                                  const bf16_t* __restrict__ w, long ldw,
+                                                                  const float* __restrict__ biasl2,
+                                                                  const float* __restrict__ info, int Mp,
+                                                                  float* __restrict__ gw, float* __restrict__ gb, int M,
+                                                                  int V) {
+  // the epilogue reuses the ring for the second token half's partial sums (2 x 65 x 64 floats)
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * T_STAGE];
+  static_assert(2 * 65 * 64 * 4 <= NBUF * T_STAGE, "partial sums must fit in the ring");
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int vs = wv & 1, i2 = wv >> 1;  // vocabulary sub-block, token half of every tile
+  const int nt = Mp / 64;
+  auto issue = [&](int qt) {  // token tile qt -> slot qt % NBUF; waves 0..2 fetch lse, scale, label
+    uint8_t* slot = smem + (qt % NBUF) * T_STAGE;
+    dma_block(t, ldt, qt * 64, M, slot, wv, lane);
+    if (wv < 3) dma_f32x64(info + (long)wv * Mp + qt * 64, slot + 2 * TILE_BYTES + wv * 256, lane);
+  };
+  issue(0);
+
+  const int vbase = blockIdx.x * DW_ROWS + 32 * vs;
+  const int v = vbase + r;
+  bf16x8 wf[8];
+  load_row_frags(w, ldw, min(v, V - 1), hh, wf);
+  float bl = biasl2[v];  // padded to whole tiles: -1e30 past V - 1
+  settle(bl);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) settle(wf[ks]);
+  floatx16 acc[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) zero(acc[c]);
+  float db = 0.f;
+
+  wait_vm_all();
+  for (int qt = 0; qt < nt; ++qt) {
+    ring_wait();
+    __syncthreads();
+    if (qt + 1 < nt) issue(qt + 1);
+    const uint8_t* Ts = smem + (qt % NBUF) * T_STAGE;
+    const float* lse_s = reinterpret_cast<const float*>(Ts + 2 * TILE_BYTES) + 32 * i2;
+    const float* gs_s = lse_s + 64;
+    const int* lab_s = reinterpret_cast<const int*>(lse_s + 128);
+    floatx16 sc;
+    zero(sc);
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) sc = mfma32(block_row_frag(Ts, 32 * i2 + r, ks, hh), wf[ks], sc);
+    if (__ballot((unsigned)(lab_s[r] - vbase) < 32u) == 0) {  // no label among this wave's vocabulary rows
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int tok = crow(i, hh);
+        sc[i] = __builtin_amdgcn_exp2f(fmaf(sc[i], LOG2E, bl - lse_s[tok])) * gs_s[tok];
+        db += sc[i];
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const int tok = crow(i, hh);
+        const float p = __builtin_amdgcn_exp2f(fmaf(sc[i], LOG2E, bl - lse_s[tok]));
+        sc[i] = (p - (lab_s[tok] == v ? 1.f : 0.f)) * gs_s[tok];
+        db += sc[i];
+      }
+    }
+#pragma unroll
+    for (int ss = 0; ss < 2; ++ss) {
+      const bf16x8 pb = pack_acc(sc, ss);
+#pragma unroll
+      for (int c = 0; c < 4; ++c) acc[c] = mfma32(block_tr(Ts, 32 * i2 + 16 * ss, hh, c, lane), pb, acc[c]);
+    }
+  }
+  db = half_sum(db);
+  __syncthreads();  // every wave is done with the ring before the epilogue reuses it
+  float* red = reinterpret_cast<float*>(smem) + vs * 65 * 64 + lane;  // [vs][65 values][64 lanes]
+  if (i2 == 1) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) red[(16 * c + i) * 64] = acc[c][i];
+    red[64 * 64] = db;
+  }
+  __syncthreads();
+  if (i2 == 0 && v < V) {
+    float* gp = gw + (long)v * E;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {  // columns 32 c + 8 q + 4 hh + (0..3) of vocabulary row v
+        float4* p = reinterpret_cast<float4*>(gp + 32 * c + 8 * q + 4 * hh);
+        float4 g = *p;
+        g.x += acc[c][4 * q] + red[(16 * c + 4 * q) * 64];
+        g.y += acc[c][4 * q + 1] + red[(16 * c + 4 * q + 1) * 64];
+        g.z += acc[c][4 * q + 2] + red[(16 * c + 4 * q + 2) * 64];
+        g.w += acc[c][4 * q + 3] + red[(16 * c + 4 * q + 3) * 64];
+        *p = g;
+      }
+    if (hh == 0) gb[v] += db + red[64 * 64];
+  }
+}
+
+}  // namespace
+
+// What the kernels need: the embedding size they are written for and 16-byte aligned rows.
+static bool mlm_xent_ok(const DlMlmXent& a) {
+  return a.E == E && a.M >= 0 && a.V >= 1 && a.ldt % 8 == 0 && a.ldw % 8 == 0 && a.lddt % 8 == 0 &&
+         (uintptr_t)a.t % 16 == 0 && (uintptr_t)a.w % 16 == 0 && (uintptr_t)a.dt % 16 == 0 && (uintptr_t)a.gw % 16 == 0;
+}
+
+static void mlm_bias(const DlMlmXent& a, hipStream_t st) {
+  const int Vp = (a.V + 63) / 64 * 64;
+  mlm_bias_kernel<<<(Vp + 255) / 256, 256, 0, st>>>(a.bias, a.bias_bf16, a.bias_ws, a.V, Vp);
+}
+
+int dl_mlm_xent_fwd(const DlMlmXent& a, hipStream_t st) {
+  if (!mlm_xent_ok(a)) return -1;
+  if (a.M > 0) {
+    mlm_bias(a, st);
+    mlm_xent_fwd_kernel<<<(a.M + FWD_ROWS - 1) / FWD_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.labels,
+                                                                         a.lse, a.row_loss, a.M, a.V, a.ignore_index);
+  }
+  mlm_loss_kernel<<<1, 1024, 0, st>>>(a.row_loss, a.labels, a.M, a.ignore_index, a.loss);
+  return 0;
+}
+
+int dl_mlm_xent_bwd(const DlMlmXent& a, hipStream_t st) {
+  if (!mlm_xent_ok(a) || (a.gw == nullptr) != (a.gb == nullptr)) return -1;
+  if (a.M == 0) return 0;
+  const int Mp = (a.M + 63) / 64 * 64;
+  mlm_bias(a, st);
+  mlm_rows_kernel<<<1, 1024, 0, st>>>(a.lse, a.labels, a.gloss, a.M, Mp, a.ignore_index, a.row_ws);
+  mlm_xent_bwd_dt_kernel<<<(a.M + DT_ROWS - 1) / DT_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.row_ws, Mp,
+                                                                        a.dt, a.lddt, a.M, a.V);
+  if (a.gw)
+    mlm_xent_bwd_dw_kernel<<<(a.V + DW_ROWS - 1) / DW_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.row_ws,
+                                                                          Mp, a.gw, a.gb, a.M, a.V);
+  return 0;
+}

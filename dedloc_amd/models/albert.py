@@ -151,6 +151,10 @@ _SHARED_WGRAD = True
 # row): _AlbertLastLayerFn over ops.attn_fwd_q / attn_bwd_q.  Head_dim 64 on rectangular batches;
 # everything else, and every other model class, runs the full layer.
 _LAST_LAYER_ROWS = True
+# AlbertForPreTraining's MLM loss on ops.mlm_cross_entropy: the tied decoder GEMM and the
+# cross-entropy in one set of kernels that keep the logits fp32 and never store them.  Embedding
+# size 128 only; a call that asks for the logits (return_logits) and evaluate_batch keep the decoder GEMM.
+_FUSED_MLM_LOSS = True
 
 
 class _AlbertLayerFn(torch.autograd.Function):
@@ -737,17 +741,29 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
             return (row0[:, None] + mlm_positions).reshape(-1), mlm_labels.reshape(-1)
         return None, None
 
-    def _mlm_logits(self, h, rows):
+    def _mlm_transform(self, h, rows):
+        """predictions.dense -> gelu_new -> LayerNorm on the selected rows: the decoder's input [M, E]."""
         c, f = self.config, self.flat
         hm = h.index_select(0, rows)
         p = "predictions."
         t = ops.linear(hm, f.w(p + "dense.weight"), f.w(p + "dense.bias"), f.g(p + "dense.weight"),
                        f.g(p + "dense.bias"))
         t = ops.gelu_new(t)
-        t = ops.add_layernorm(t, None, f.p(p + "LayerNorm.weight"), f.p(p + "LayerNorm.bias"),
-                              f.g(p + "LayerNorm.weight"), f.g(p + "LayerNorm.bias"), c.layer_norm_eps)
-        wname = "albert.embeddings.word_embeddings.weight"
-        return ops.linear(t, f.w(wname), f.w(p + "bias"), f.g(wname), f.g(p + "bias"))
+        return ops.add_layernorm(t, None, f.p(p + "LayerNorm.weight"), f.p(p + "LayerNorm.bias"),
+                                 f.g(p + "LayerNorm.weight"), f.g(p + "LayerNorm.bias"), c.layer_norm_eps)
+
+    def _mlm_decoder(self):
+        """(weight, bias, their fp32 gradient views) of the decoder tied to the word embeddings"""
+        f, wname, bname = self.flat, "albert.embeddings.word_embeddings.weight", "predictions.bias"
+        return f.w(wname), f.w(bname), f.g(wname), f.g(bname)
+
+    def _mlm_logits(self, h, rows):
+        return ops.linear(self._mlm_transform(h, rows), *self._mlm_decoder())
+
+    def _mlm_loss(self, h, rows, tgt):
+        """The fused decoder + cross-entropy (ops.mlm_cross_entropy): no [M, V] logits."""
+        w, b, gw, gb = self._mlm_decoder()
+        return ops.mlm_cross_entropy(self._mlm_transform(h, rows), w, b, tgt, gw, gb)
 
     def _sop_logits(self, h, B, Sp, pk, row0):
         c, f = self.config, self.flat
@@ -807,12 +823,15 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels, sel)
         loss = None
         if rows is not None:
-            logits = self._mlm_logits(h, rows)
-            mlm_loss = ops.cross_entropy(logits, tgt)
+            if _FUSED_MLM_LOSS and self.config.embedding_size == 128 and not return_logits:
+                mlm_loss = self._mlm_loss(h, rows, tgt)
+            else:
+                logits = self._mlm_logits(h, rows)
+                mlm_loss = ops.cross_entropy(logits, tgt)
+                if return_logits:
+                    out["prediction_logits_masked"] = logits
             out["mlm_loss"] = mlm_loss
             loss = mlm_loss
-            if return_logits:
-                out["prediction_logits_masked"] = logits
         # ---- SOP head on [CLS]
         sop_logits = self._sop_logits(h, B, Sp, pk, row0)
         out["sop_logits"] = sop_logits

@@ -329,6 +329,35 @@ def cross_entropy(logits, labels, ignore_index=-100):
     return _CrossEntropy.apply(logits.contiguous(), labels.reshape(-1).contiguous(), ignore_index)
 
 
+class _MlmCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, t, w, bias, labels, gw, gb, ignore_index):
+        loss, lse = OPS.mlm_xent_fwd(t, w, bias, labels, ignore_index)
+        ctx.save_for_backward(t, w, bias, labels, lse)
+        ctx.gw, ctx.gb, ctx.ignore_index = gw, gb, ignore_index
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        t, w, bias, labels, lse = ctx.saved_tensors
+        dt = OPS.mlm_xent_bwd(t, w, bias, labels, lse, dloss.reshape(1).float(), ctx.gw, ctx.gb, ctx.ignore_index)
+        return dt, None, None, None, None, None, None
+
+
+def mlm_cross_entropy(t, w, bias, labels, gw=None, gb=None, ignore_index=-100):
+    """``cross_entropy(linear(t, w, bias), labels)`` for the tied MLM decoder without the [M, V]
+    logits: t [M, 128] bf16, w [V, 128] bf16, bias [V].  The logits stay fp32 inside the kernels
+    (the composed path rounds them to bf16); the backward recomputes them from t, the saved
+    log-sum-exp and the labels, returns dt and adds the weight and bias gradients into the fp32
+    views ``gw`` [V, 128] / ``gb`` [V] (both or neither; without them only dt is computed)."""
+    if t.dim() != 2 or t.shape[1] != 128 or w.shape[1] != 128:
+        raise ValueError(f"mlm_cross_entropy needs an embedding size of 128, got t {tuple(t.shape)}, w {tuple(w.shape)}")
+    if (gw is None) != (gb is None):
+        raise ValueError("mlm_cross_entropy: gw and gb come together")
+    return _MlmCrossEntropy.apply(t.contiguous(), w, bias.contiguous(), labels.reshape(-1).contiguous(), gw, gb,
+                                  ignore_index)
+
+
 @torch.no_grad()
 def eval_cross_entropy(logits, labels, ignore_index=-100, topk=(1, 5)):
     """Evaluation cross-entropy over rows whose label != ignore_index, forward only (the

@@ -43,6 +43,9 @@ _SCHEMAS = [
     "embed_bwd(Tensor ds, Tensor ids, Tensor? tt, Tensor(a!) dwemb, Tensor(b!) dpemb, Tensor(c!) dtemb, int S) -> ()",
     "xent_fwd_bwd(Tensor logits, Tensor labels, bool inplace, int ignore_index) -> (Tensor, Tensor)",
     "xent_eval(Tensor logits, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
+    "mlm_xent_fwd(Tensor t, Tensor w, Tensor bias, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
+    "mlm_xent_bwd(Tensor t, Tensor w, Tensor bias, Tensor labels, Tensor lse, Tensor gloss, Tensor(a!)? gw, "
+    "Tensor(b!)? gb, int ignore_index) -> Tensor",
     "knn_topk(Tensor q, Tensor bank, int k, int splits=0) -> (Tensor, Tensor)",
     "knn_vote(Tensor vals, Tensor idx, Tensor bank_labels, Tensor targets, int num_classes, float sigma) "
     "-> (Tensor, Tensor)",
@@ -156,6 +159,9 @@ def native_loaded() -> bool:
 # ---------------------------------------------------------------------------------------------
 def _bf(x):
     return x.to(torch.bfloat16)
+
+
+_LOG2E = math.log2(math.e)
 
 
 @_impl("layernorm_fwd")
@@ -535,6 +541,40 @@ def _xent_eval_cpu(logits, labels, ignore_index):
     loss = torch.where(valid, loss, torch.where(lab == ignore_index, 0.0, float("nan")).float())
     rank = torch.where(valid, rank, torch.full_like(rank, -1))
     return loss.float(), rank.to(torch.int32)
+
+
+@_impl("mlm_xent_fwd")
+def _mlm_xent_fwd_cpu(t, w, bias, labels, ignore_index):
+    """logits = t w^T + bias in fp32 (never rounded to bf16): the mean loss over the live rows (0
+    without one) and lse [M] in log2 units, as the kernel stores it."""
+    x = t.float() @ w.float().t() + bias.float()
+    lab = labels.reshape(-1)
+    valid = lab != ignore_index
+    lse = torch.logsumexp(x, -1)
+    safe = torch.where(valid, lab, torch.zeros_like(lab))
+    rows = (lse - x.gather(1, safe[:, None]).squeeze(1)) * valid
+    cnt = int(valid.sum())
+    return (rows.sum() / cnt if cnt > 0 else rows.sum() * 0.0).float(), (lse * _LOG2E).float()
+
+
+@_impl("mlm_xent_bwd")
+def _mlm_xent_bwd_cpu(t, w, bias, labels, lse, gloss, gw, gb, ignore_index):
+    """dS = (softmax - onehot) gloss / live rows, rounded to bf16 as the kernels pack it: returns
+    dt = dS w (bf16) and adds dS^T t into gw, the column sums of dS into gb."""
+    x = t.float() @ w.float().t() + bias.float()
+    lab = labels.reshape(-1)
+    valid = lab != ignore_index
+    cnt = int(valid.sum())
+    scale = gloss.reshape(()).float() / cnt if cnt > 0 else torch.zeros(())
+    ds = torch.exp2(x * _LOG2E - lse[:, None])
+    ds[torch.arange(x.shape[0]), torch.where(valid, lab, torch.zeros_like(lab))] -= 1.0
+    ds = ds * valid[:, None] * scale
+    if gb is not None:
+        gb.add_(ds.sum(0))
+    ds = _bf(ds).float()
+    if gw is not None:
+        gw.add_(ds.t() @ t.float())
+    return _bf(ds @ w.float())
 
 
 @_impl("knn_topk")
