@@ -5,6 +5,10 @@ the head's step.  The phases overlap in the real epoch (the stream decodes ahead
 asynchronous), so the epoch is bounded by the slowest of them, not by their sum.
 
     python bench/swav_linear_epoch.py [--images 10000] [--batch 256] [--classes 10] [--out FILE]
+                                      [--protocol res5_avgpool|eval_mlp]
+
+``--protocol eval_mlp``: the five-head protocol (forward = the trunk with its five taps, head = the
+five pool / BatchNorm / Linear heads' steps).
 """
 import argparse
 import json
@@ -37,16 +41,23 @@ def main():
     ap.add_argument("--classes", type=int, default=10)
     ap.add_argument("--workers", type=int, default=8)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--protocol", default="res5_avgpool", choices=("res5_avgpool", "eval_mlp"))
     args = ap.parse_args()
     import dedloc_amd.ops as dops  # noqa: F401
     from dedloc_amd.data.image_folder import ImageFolderDataset, ImageFolderLabelledStream
     from dedloc_amd.models.resnet_swav import SwAVModel
-    from dedloc_amd.training.swav_linear import LinearProbe, train_linear
+    from dedloc_amd.training.swav_linear import EvalMLP, LinearProbe, train_linear
 
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
     model = SwAVModel().to(dev)
     trunk = model.frozen_trunk()
+    if args.protocol == "eval_mlp":
+        trunk = trunk.forward_features
+
+    def new_probe():
+        return EvalMLP(args.classes, device=dev) if args.protocol == "eval_mlp" else LinearProbe(args.classes, device=dev)
+
     with tempfile.TemporaryDirectory() as root:
         t0 = time.perf_counter()
         _folder(root, args.images, args.classes)
@@ -70,7 +81,7 @@ def main():
             pass
         torch.cuda.synchronize()
         data_s = time.perf_counter() - t0
-        probe = LinearProbe(args.classes, device=dev)
+        probe = new_probe()
         probe.train_step(f, y, 0.0)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -91,12 +102,13 @@ def main():
 
         s = stream()
         t0 = time.perf_counter()
-        train_linear(trunk, s, _Short(), args.classes, dict(NUM_EPOCHS=1, BATCH_SIZE=args.batch), dev)
+        train_linear(trunk, s, _Short(), args.classes, dict(NUM_EPOCHS=1, BATCH_SIZE=args.batch), dev,
+                     probe=new_probe())
         torch.cuda.synchronize()
         epoch_s = time.perf_counter() - t0
         s.close()
     phases = {"data": data_s, "forward": fwd_s, "head": head_s}
-    out = {"bench": "swav_linear_epoch", "images": args.images, "batch": args.batch, "classes": args.classes,
+    out = {"bench": "swav_linear_epoch", "protocol": args.protocol, "images": args.images, "batch": args.batch, "classes": args.classes,
            "steps": steps, "workers": args.workers, "epoch_s": round(epoch_s, 3),
            "images_per_s": round(args.images / epoch_s, 1), "phase_s": {k: round(v, 3) for k, v in phases.items()},
            "bound_by": max(phases, key=phases.get), "folder_generation_s": round(gen_s, 1),

@@ -13,6 +13,14 @@ trunk's pooled features (``training.swav_linear``) with the config's ``LINEAR_EV
 (NUM_EPOCHS, BATCH_SIZE, TEST_EVERY_NUM_EPOCH, MAX_TRAIN_IMAGES, MAX_TEST_IMAGES, CROP_SIZE, RESIZE,
 CENTER_CROP, BASE_LR, SCHEDULE, VALUES, MILESTONES, ...), appends one JSON line per evaluation to
 ``METRICS_FILE`` and prints the final one.
+
+``+config.LINEAR_EVAL.PROTOCOL=eval_mlp`` runs the reference's five-head protocol
+(``eval_resnet_8gpu_transfer_in1k_linear``) instead: one head on each of conv1 and res2 .. res5
+(average pool -> BatchNorm -> Linear), trained side by side on one frozen forward, with
+``linear_top1_<tap>`` / ``linear_top5_<tap>`` / ``linear_loss_<tap>`` per evaluation (the unsuffixed
+keys are res5's).  ``LINEAR_EVAL.POOLS`` ({tap: [k, stride, pad]}) overrides the reference's pools;
+``LINEAR_EVAL.SAVE_HEADS`` / ``LOAD_HEADS`` name a file the trained heads are written to / read from
+(Linear weights in ``torch.flatten``'s NCHW order; a file of the other protocol is refused).
 """
 from __future__ import annotations
 

@@ -1407,6 +1407,104 @@ at::Tensor avgpool_bwd(const at::Tensor& dy_in, int64_t H, int64_t W) {
   return dx;
 }
 
+// AvgPool2d(k, stride, pad) with torch's defaults over channels-last bf16 and the per-channel sum /
+// sum of squares of the pooled values (pool_eval.hip): (y fp32 channels-last, sum [C], sumsq [C])
+std::tuple<at::Tensor, at::Tensor, at::Tensor> avgpool_bn_stats(const at::Tensor& x, int64_t k, int64_t stride,
+                                                                int64_t pad) {
+  expect_nhwc(x, "x");
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  TORCH_CHECK(C % 8 == 0, "avgpool_bn_stats: C must be a multiple of 8, got ", C);
+  TORCH_CHECK(k >= 1 && stride >= 1 && pad >= 0, "avgpool_bn_stats: k / stride / pad");
+  TORCH_CHECK(pad <= k / 2, "avgpool_bn_stats: pad should be at most half of the kernel size, got pad ", pad,
+              " and k ", k);
+  TORCH_CHECK(H + 2 * pad >= k && W + 2 * pad >= k, "avgpool_bn_stats: the window (", k,
+              ") is larger than the padded input (", H + 2 * pad, " x ", W + 2 * pad, ")");
+  const int64_t OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+  const int groups = dl_avgpool_stats_groups((int)N, (int)H, (int)W, (int)C, (int)k, (int)stride, (int)pad);
+  TORCH_CHECK(groups > 0, "avgpool_bn_stats: shape outside the kernel's contract (W <= 256 covered input columns, "
+                          "OW <= 96, N <= 65535)");
+  auto fopt = x.options().dtype(at::kFloat);
+  auto y = at::empty({N, C, OH, OW}, fopt, at::MemoryFormat::ChannelsLast);
+  auto part = at::empty({groups, 2, C}, fopt);
+  auto sums = at::empty({2, C}, fopt);
+  check(dl_avgpool_stats_fwd(cbf(x), f32(y), f32(part), f32(sums), (int)N, (int)H, (int)W, (int)C, (int)k, (int)stride,
+                             (int)pad, cur_stream(x)),
+        "avgpool_bn_stats");
+  return {y, sums.select(0, 0), sums.select(0, 1)};
+}
+
+// BatchNorm of avgpool_bn_stats' fp32 pooled tensor (pool_eval.hip).  bn_fwd_f32: train mode over its sum /
+// sumsq [C]: (f bf16 channels-last, mean [1, C], rstd [1, C]); one momentum update of the running
+// statistics, by bn_fwd's conventions.  bn_eval_f32: f from the running statistics.  bn_bwd_f32: the
+// parameter gradients for dy, added into dgamma / dbeta (the pooled input takes no gradient).
+inline int64_t expect_pooled(const at::Tensor& y, const char* op) {
+  TORCH_CHECK(y.is_cuda() && y.scalar_type() == at::kFloat && y.dim() == 4 &&
+                  y.is_contiguous(at::MemoryFormat::ChannelsLast),
+              op, ": y must be a channels-last fp32 [N, C, H, W] GPU tensor");
+  TORCH_CHECK(y.size(1) % 8 == 0 && y.numel() > 0, op, ": C must be a multiple of 8");
+  return y.size(1);
+}
+inline void expect_c(const at::Tensor& t, int64_t C, const char* name) {
+  expect(t, at::kFloat, name);
+  TORCH_CHECK(t.numel() == C && t.is_contiguous(), name, " must hold C contiguous floats");
+}
+
+std::tuple<at::Tensor, at::Tensor, at::Tensor> bn_fwd_f32(const at::Tensor& y, const at::Tensor& sum,
+                                                          const at::Tensor& sumsq, const at::Tensor& gamma,
+                                                          const at::Tensor& beta,
+                                                          const c10::optional<at::Tensor>& running_mean,
+                                                          const c10::optional<at::Tensor>& running_var, double eps,
+                                                          double momentum) {
+  const int64_t C = expect_pooled(y, "bn_fwd_f32"), R = y.numel() / C;
+  expect_c(sum, C, "sum");
+  expect_c(sumsq, C, "sumsq");
+  expect_c(gamma, C, "gamma");
+  expect_c(beta, C, "beta");
+  TORCH_CHECK(running_mean.has_value() == running_var.has_value(), "bn_fwd_f32: running_mean and running_var come together");
+  if (running_mean.has_value()) {
+    expect_c(*running_mean, C, "running_mean");
+    expect_c(*running_var, C, "running_var");
+  }
+  auto f = at::empty(y.sizes(), y.options().dtype(at::kBFloat16), at::MemoryFormat::ChannelsLast);
+  auto stats = at::empty({2, 1, C}, gamma.options());
+  check(dl_bn_f32_fwd(f32(y), bf(f), f32(sum), f32(sumsq), f32(gamma), f32(beta), f32(stats), f32(stats) + C,
+                      running_mean.has_value() ? f32(*running_mean) : nullptr,
+                      running_mean.has_value() ? f32(*running_var) : nullptr, R, (int)C, (float)eps, (float)momentum,
+                      cur_stream(y)),
+        "bn_fwd_f32");
+  return {f, stats.select(0, 0), stats.select(0, 1)};
+}
+
+at::Tensor bn_eval_f32(const at::Tensor& y, const at::Tensor& gamma, const at::Tensor& beta,
+                       const at::Tensor& running_mean, const at::Tensor& running_var, double eps) {
+  const int64_t C = expect_pooled(y, "bn_eval_f32");
+  expect_c(gamma, C, "gamma");
+  expect_c(beta, C, "beta");
+  expect_c(running_mean, C, "running_mean");
+  expect_c(running_var, C, "running_var");
+  auto f = at::empty(y.sizes(), y.options().dtype(at::kBFloat16), at::MemoryFormat::ChannelsLast);
+  check(dl_bn_f32_eval(f32(y), bf(f), f32(gamma), f32(beta), f32(running_mean), f32(running_var), y.numel() / C, (int)C,
+                       (float)eps, cur_stream(y)),
+        "bn_eval_f32");
+  return f;
+}
+
+void bn_bwd_f32(const at::Tensor& dy_in, const at::Tensor& y, const at::Tensor& mean, const at::Tensor& rstd,
+                at::Tensor dgamma, at::Tensor dbeta) {
+  const int64_t C = expect_pooled(y, "bn_bwd_f32"), R = y.numel() / C;
+  const at::Tensor dy = dy_in.contiguous(at::MemoryFormat::ChannelsLast);
+  expect_nhwc(dy, "dy");
+  TORCH_CHECK(dy.sizes() == y.sizes(), "bn_bwd_f32: dy must have y's shape");
+  expect_c(mean, C, "mean");
+  expect_c(rstd, C, "rstd");
+  expect_c(dgamma, C, "dgamma");
+  expect_c(dbeta, C, "dbeta");
+  auto part = at::empty({dl_bn_f32_bwd_groups(R), 2, C}, mean.options());
+  check(dl_bn_f32_bwd(cbf(dy), f32(y), f32(mean), f32(rstd), f32(part), f32(dgamma), f32(dbeta), R, (int)C,
+                      cur_stream(y)),
+        "bn_bwd_f32");
+}
+
 std::tuple<at::Tensor, at::Tensor> l2norm_fwd(const at::Tensor& x_in, double eps) {
   const at::Tensor x = x_in.contiguous();
   expect(x, at::kBFloat16, "x");
@@ -2017,6 +2115,10 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("maxpool_bwd", &maxpool_bwd);
   m.impl("avgpool_fwd", &avgpool_fwd);
   m.impl("avgpool_bwd", &avgpool_bwd);
+  m.impl("avgpool_bn_stats", &avgpool_bn_stats);
+  m.impl("bn_fwd_f32", &bn_fwd_f32);
+  m.impl("bn_eval_f32", &bn_eval_f32);
+  m.impl("bn_bwd_f32", &bn_bwd_f32);
   m.impl("l2norm_fwd", &l2norm_fwd);
   m.impl("l2norm_bwd", &l2norm_bwd);
   m.impl("multicrop", &multicrop);

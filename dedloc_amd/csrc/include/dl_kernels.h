@@ -319,6 +319,24 @@ int dl_avgpool_bwd(const bf16_t* dy, bf16_t* dx, int N, int HW, int C, hipStream
 int dl_l2norm_fwd(const bf16_t* x, bf16_t* y, float* rinv, int rows, int D, float eps, hipStream_t st);
 int dl_l2norm_bwd(const bf16_t* dy, const bf16_t* y, const float* rinv, bf16_t* dx, int rows, int D, hipStream_t st);
 
+// pool_eval.hip (the linear evaluation's strided, padded average pools with BatchNorm statistics):
+// y [N, OH, OW, C] fp32, sums [2, C] fp32 (sum | sum of squares of the pooled values), part a scratch
+// of dl_avgpool_stats_groups(...) * 2 * C floats; -1: a shape outside the kernel's contract
+int dl_avgpool_stats_groups(int N, int H, int W, int C, int k, int s, int p);
+int dl_avgpool_stats_fwd(const bf16_t* x, float* y, float* part, float* sums, int N, int H, int W, int C, int k, int s,
+                         int p, hipStream_t st);
+// BatchNorm of that fp32 y to bf16 f: train mode over sum / sumsq [C] (mean / rstd out, one momentum
+// update of run_mean / run_var when given), evaluation mode over the running statistics, and the
+// parameter gradients dgamma / dbeta += (part: dl_bn_f32_bwd_groups(R) * 2 * C floats of scratch)
+int dl_bn_f32_fwd(const float* y, bf16_t* f, const float* sum, const float* sumsq, const float* gamma,
+                  const float* beta, float* mean, float* rstd, float* run_mean, float* run_var, long R, int C, float eps,
+                  float momentum, hipStream_t st);
+int dl_bn_f32_eval(const float* y, bf16_t* f, const float* gamma, const float* beta, const float* run_mean,
+                   const float* run_var, long R, int C, float eps, hipStream_t st);
+int dl_bn_f32_bwd_groups(long R);
+int dl_bn_f32_bwd(const bf16_t* dy, const float* y, const float* mean, const float* rstd, float* part, float* dgamma,
+                  float* dbeta, long R, int C, hipStream_t st);
+
 // gemm_small.hip: any-shape / any-stride bf16 MFMA GEMM (STORE: bf16 C (+bias)(+R); F32: fp32 Cf (+)=).
 // g.splits > 1 splits the reduction into fp32 slabs: ws must hold splits * M * N floats.
 // stats (STORE, splits 1 only): BatchNorm statistics of the stored values as DL_EPI_STATS

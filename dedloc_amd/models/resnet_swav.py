@@ -24,7 +24,7 @@ in the consuming 1x1 convolution's data gradient (measured in profiles/README.md
 """
 from __future__ import annotations
 
-from typing import List, Sequence
+from typing import Dict, List, Sequence
 
 import contextlib
 import os
@@ -672,6 +672,7 @@ class FrozenTrunk:
     """
 
     CLASSES = ("stem", "3x3", "1x1", "strided1x1")
+    TAPS = ("conv1", "res2", "res3", "res4", "res5")  # forward_features' names, in forward order
 
     def __init__(self, trunk: "ResNet50Trunk", fused=True):
         self.fused = frozenset(self.CLASSES if fused is True else (() if not fused else fused))
@@ -680,11 +681,13 @@ class FrozenTrunk:
         with torch.no_grad():
             self.stem = self._snap(trunk.conv1, trunk.bn1)
             self.blocks = []
-            for stage in (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4):
+            self.stage_ends = {}  # tap name -> number of blocks run when that stage's output stands
+            for name, stage in zip(self.TAPS[1:], (trunk.layer1, trunk.layer2, trunk.layer3, trunk.layer4)):
                 for b in stage:
                     down = None if b.downsample is None else self._snap(b.downsample[0], b.downsample[1])
                     self.blocks.append((self._snap(b.conv1, b.bn1), self._snap(b.conv2, b.bn2),
                                         self._snap(b.conv3, b.bn3), down))
+                self.stage_ends[len(self.blocks)] = name
 
     @staticmethod
     def _snap(conv, bn):
@@ -711,6 +714,33 @@ class FrozenTrunk:
             idt = x if down is None else self._conv(x, down)
             x = self._conv(self._conv(self._conv(x, c1), c2), c3, idt)
         return torch.ops.dedloc.avgpool_fwd(x)
+
+    @torch.no_grad()
+    def forward_features(self, x: torch.Tensor, taps: Sequence[str] = TAPS) -> Dict[str, torch.Tensor]:
+        """The intermediate activations the five-head linear evaluation reads, by name: ``conv1`` (the
+        stem's conv + BN + ReLU, before the max pool) and ``res2`` .. ``res5`` (the outputs of layer1
+        .. layer4), each the ``[N, C, H, W]`` bf16 channels-last tensor the forward produced itself
+        (no copy).  The forward stops after the last stage asked for."""
+        unknown = [t for t in taps if t not in self.TAPS]
+        if unknown or not taps:
+            raise ValueError(f"taps: names out of {self.TAPS}, got {list(taps)}")
+        x = _require_nhwc_bf16(x, "FrozenTrunk input")
+        out, last = {}, max(self.TAPS.index(t) for t in taps)
+        x = self._conv(x, self.stem)
+        if "conv1" in taps:
+            out["conv1"] = x
+        if last == 0:
+            return out
+        x = torch.ops.dedloc.maxpool_fwd(x)[0]
+        for i, (c1, c2, c3, down) in enumerate(self.blocks):
+            idt = x if down is None else self._conv(x, down)
+            x = self._conv(self._conv(self._conv(x, c1), c2), c3, idt)
+            name = self.stage_ends.get(i + 1)
+            if name in taps:
+                out[name] = x
+            if name is not None and self.TAPS.index(name) == last:
+                break
+        return out
 
 
 class _HeadLinearFn(torch.autograd.Function):

@@ -401,9 +401,22 @@ def knn_classify(q, bank, bank_labels, targets, num_classes, k=200, sigma=0.1, s
             "rank": rank}
 
 
+@torch.no_grad()
+def avgpool_bn_stats(x, k, stride, pad=0):
+    """``AvgPool2d(k, stride, pad)`` with torch's defaults (padded taps are zero and count in the
+    divisor ``k*k``; the output size is floored) over ``x`` [N, C, H, W] bf16 channels-last, and the
+    train-mode BatchNorm statistics of the result in the same pass: ``y`` [N, C, OH, OW] fp32
+    channels-last, ``sum`` [C] and ``sumsq`` [C] fp32 (the inputs of ``OPS.bn_fwd_f32``, the
+    BatchNorm of y to bf16).  y is fp32 because the BatchNorm behind it takes
+    a mean off that can be many times the batch spread it then divides by.  Forward only (the linear evaluation's trunk is frozen); two
+    calls give the same bits.  Raises ``RuntimeError`` for an input that is not bf16 channels-last,
+    ``C % 8 != 0``, ``pad > k // 2`` or a window larger than the padded input."""
+    return OPS.avgpool_bn_stats(x, int(k), int(stride), int(pad))
+
+
 __all__ = [
     "linear", "gelu_new", "tanh", "add_layernorm", "attention", "embed_layernorm", "cross_entropy",
-    "eval_cross_entropy", "knn_topk", "knn_classify", "OPS",
+    "eval_cross_entropy", "knn_topk", "knn_classify", "avgpool_bn_stats", "OPS",
     "load_native", "native_loaded",
 ]
 

@@ -78,6 +78,11 @@ _SCHEMAS = [
     "maxpool_bwd(Tensor dy, Tensor arg, int H, int W) -> Tensor",
     "avgpool_fwd(Tensor x) -> Tensor",
     "avgpool_bwd(Tensor dy, int H, int W) -> Tensor",
+    "avgpool_bn_stats(Tensor x, int k, int stride, int pad) -> (Tensor, Tensor, Tensor)",
+    "bn_fwd_f32(Tensor y, Tensor sum, Tensor sumsq, Tensor gamma, Tensor beta, Tensor(a!)? running_mean, "
+    "Tensor(b!)? running_var, float eps, float momentum) -> (Tensor, Tensor, Tensor)",
+    "bn_eval_f32(Tensor y, Tensor gamma, Tensor beta, Tensor running_mean, Tensor running_var, float eps) -> Tensor",
+    "bn_bwd_f32(Tensor dy, Tensor y, Tensor mean, Tensor rstd, Tensor(a!) dgamma, Tensor(b!) dbeta) -> ()",
     "l2norm_fwd(Tensor x, float eps) -> (Tensor, Tensor)",
     "l2norm_bwd(Tensor dy, Tensor y, Tensor rinv) -> Tensor",
     "multicrop(Tensor pool, Tensor params, int size, int rad, float[] mean, float[] std) -> Tensor",
@@ -949,6 +954,51 @@ def _avgpool_fwd_cpu(x):
 def _avgpool_bwd_cpu(dy, H, W):
     return (dy.float()[:, :, None, None] / (H * W)).expand(dy.shape[0], dy.shape[1], H, W).to(dy.dtype).contiguous(
         memory_format=torch.channels_last)
+
+
+@_impl("avgpool_bn_stats")
+def _avgpool_bn_stats_cpu(x, k, stride, pad):
+    if x.dtype != torch.bfloat16:
+        raise RuntimeError(f"avgpool_bn_stats: x has dtype {x.dtype}, expected torch.bfloat16")
+    if x.dim() != 4 or not x.is_contiguous(memory_format=torch.channels_last):
+        raise RuntimeError("avgpool_bn_stats: x must be a channels-last [N, C, H, W] tensor")
+    if x.shape[1] % 8:
+        raise RuntimeError(f"avgpool_bn_stats: C must be a multiple of 8, got {x.shape[1]}")
+    if k < 1 or stride < 1 or pad < 0 or pad > k // 2:
+        raise RuntimeError(f"avgpool_bn_stats: pad should be at most half of the kernel size, got k {k}, stride "
+                           f"{stride}, pad {pad}")
+    if x.shape[2] + 2 * pad < k or x.shape[3] + 2 * pad < k:
+        raise RuntimeError(f"avgpool_bn_stats: the window ({k}) is larger than the padded input")
+    v = F.avg_pool2d(x.float(), k, stride, pad).contiguous(memory_format=torch.channels_last)
+    return v, v.sum(dim=(0, 2, 3)), (v * v).sum(dim=(0, 2, 3))
+
+
+@_impl("bn_fwd_f32")
+def _bn_fwd_f32_cpu(y, sum, sumsq, gamma, beta, running_mean, running_var, eps, momentum):
+    C, R = y.shape[1], y.numel() // y.shape[1]
+    mean = sum / R
+    var = (sumsq / R - mean * mean).clamp_min(0)
+    rstd = torch.rsqrt(var + eps)
+    f = (y - mean.view(1, -1, 1, 1)) * (rstd * gamma).view(1, -1, 1, 1) + beta.view(1, -1, 1, 1)
+    if running_mean is not None:
+        running_mean.mul_(1 - momentum).add_(mean, alpha=momentum)
+        running_var.mul_(1 - momentum).add_(var * (R / max(R - 1, 1)), alpha=momentum)
+    return f.to(torch.bfloat16).contiguous(memory_format=torch.channels_last), mean.view(1, C), rstd.view(1, C)
+
+
+@_impl("bn_eval_f32")
+def _bn_eval_f32_cpu(y, gamma, beta, running_mean, running_var, eps):
+    g = gamma * torch.rsqrt(running_var + eps)
+    f = y * g.view(1, -1, 1, 1) + (beta - running_mean * g).view(1, -1, 1, 1)
+    return f.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
+
+
+@_impl("bn_bwd_f32")
+def _bn_bwd_f32_cpu(dy, y, mean, rstd, dgamma, dbeta):
+    g = dy.float()
+    xhat = (y - mean.view(1, -1, 1, 1)) * rstd.view(1, -1, 1, 1)
+    dgamma.add_((g * xhat).sum(dim=(0, 2, 3)))
+    dbeta.add_(g.sum(dim=(0, 2, 3)))
 
 
 @_impl("l2norm_fwd")

@@ -32,7 +32,14 @@ LINEAR_SEED = 2 ** 31 + 0xE7A4
 
 DEFAULTS = dict(NUM_EPOCHS=100, BATCH_SIZE=256, TEST_EVERY_NUM_EPOCH=1, MAX_TRAIN_IMAGES=0, MAX_TEST_IMAGES=0,
                 CROP_SIZE=224, RESIZE=256, CENTER_CROP=224, BASE_LR=0.3, BASE_LR_BATCH_SIZE=256, MOMENTUM=0.9,
-                WEIGHT_DECAY=1e-6, SCHEDULE="cosine", VALUES=None, MILESTONES=None, SEED=LINEAR_SEED)
+                WEIGHT_DECAY=1e-6, SCHEDULE="cosine", VALUES=None, MILESTONES=None, SEED=LINEAR_SEED,
+                PROTOCOL="res5_avgpool", POOLS=None, SAVE_HEADS=None, LOAD_HEADS=None)
+
+PROTOCOLS = ("res5_avgpool", "eval_mlp")
+TAPS = ("conv1", "res2", "res3", "res4", "res5")
+TAP_CHANNELS = dict(conv1=64, res2=256, res3=512, res4=1024, res5=2048)
+# the reference's pools (k, stride, pad) per tap: 9216 / 9216 / 8192 / 9216 / 8192 features at 224 pixels
+DEFAULT_POOLS = dict(conv1=(10, 10, 4), res2=(16, 8, 0), res3=(13, 5, 0), res4=(8, 3, 0), res5=(6, 1, 0))
 
 
 def learning_rate(step: int, steps_per_epoch: int, num_epochs: int, peak: float, schedule: str = "cosine",
@@ -107,6 +114,191 @@ class LinearProbe:
         return torch.stack([out["loss_sum"].double(), out["count"].double(), out["top1"].double(),
                             out["top5"].double()])
 
+    def state_dict(self) -> dict:
+        return {"protocol": "res5_avgpool", "weight": self.weight.detach()[:self.num_classes].cpu().clone(),
+                "bias": self.bias.detach()[:self.num_classes].cpu().clone()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        _check_protocol(sd, "res5_avgpool")
+        with torch.no_grad():
+            self.weight[:self.num_classes].copy_(sd["weight"])
+            self.bias[:self.num_classes].copy_(sd["bias"])
+
+
+def protocol(settings: dict) -> str:
+    p = str(settings.get("PROTOCOL") or "res5_avgpool")
+    if p not in PROTOCOLS:
+        raise ValueError(f"LINEAR_EVAL.PROTOCOL must be one of {PROTOCOLS}, got {p!r}")
+    return p
+
+
+def _check_protocol(sd: dict, want: str) -> None:
+    got = sd.get("protocol") if isinstance(sd, dict) else None
+    if got != want:
+        raise ValueError(f"linear evaluation: the head checkpoint holds protocol {got!r} "
+                         f"({'five heads' if got == 'eval_mlp' else 'one head'}), LINEAR_EVAL.PROTOCOL is {want!r}")
+
+
+def save_heads(path: str, probe) -> None:
+    torch.save(probe.state_dict(), path)
+
+
+def load_heads(path: str, probe) -> None:
+    probe.load_state_dict(torch.load(path, map_location="cpu", weights_only=True))
+
+
+def tap_shapes(size: int) -> Dict[str, tuple]:
+    """(C, H, W) of the ResNet-50 trunk's five taps for square images of ``size`` pixels."""
+    half = lambda h: (h - 1) // 2 + 1  # noqa: E731  (every stride-2 conv and the max pool: k odd, pad k // 2)
+    out, h = {"conv1": (64, half(size), half(size))}, half(half(size))
+    for i, tap in enumerate(TAPS[1:]):
+        h = h if i == 0 else half(h)
+        out[tap] = (TAP_CHANNELS[tap], h, h)
+    return out
+
+
+def resolve_pools(pools) -> Dict[str, tuple]:
+    """``LINEAR_EVAL.POOLS`` ({tap: [k, stride, pad]}, any subset of the taps) over the defaults."""
+    out = dict(DEFAULT_POOLS)
+    for tap, v in dict(pools or {}).items():
+        if tap not in TAPS or len(v) != 3:
+            raise ValueError(f"LINEAR_EVAL.POOLS: entries are <tap>: [k, stride, pad] with taps out of {TAPS}, got "
+                             f"{tap!r}: {v!r}")
+        out[tap] = tuple(int(a) for a in v)
+    return out
+
+
+class _PoolBN(torch.autograd.Function):
+    """``BatchNorm2d(AvgPool2d(x))`` in train mode on a frozen activation: ``ops.avgpool_bn_stats`` (the
+    pool and the batch statistics in one pass over x, pooled values in fp32), then ``bn_fwd_f32`` over
+    those statistics (normalise to bf16, running statistics by ``_BNAct``'s conventions).  x takes no
+    gradient, so the backward is the parameters' alone: ``bn_bwd_f32`` adds dgamma / dbeta, with xhat
+    rebuilt from the fp32 pooled values, into the parameters' fp32 ``.grad``."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, pool, eps, momentum):
+        y, s1, s2 = ops.avgpool_bn_stats(x, *pool)
+        f, mean, rstd = ops.OPS.bn_fwd_f32(y, s1, s2, gamma.detach(), beta.detach(), running_mean, running_var, eps,
+                                           momentum)
+        ctx.save_for_backward(y, mean, rstd)
+        ctx.gamma, ctx.beta = gamma, beta
+        return f
+
+    @staticmethod
+    def backward(ctx, dy):
+        y, mean, rstd = ctx.saved_tensors
+        ops.OPS.bn_bwd_f32(dy, y, mean.reshape(-1), rstd.reshape(-1), ctx.gamma.grad, ctx.beta.grad)
+        return (None,) * 8
+
+
+class EvalMLPHead:
+    """One head of the five-head protocol: pool -> BatchNorm2d over channels (train mode while
+    training, running statistics when scoring) -> flatten -> Linear.  The features enter the Linear
+    in the activations' own channels-last order, (oh, ow, c); the Linear weight is kept in that order
+    and permuted to ``torch.flatten``'s NCHW order (c, oh, ow) when saved or loaded, so a checkpoint
+    interchanges with the reference's and no activation is ever permuted."""
+
+    def __init__(self, tap: str, shape, pool, num_classes: int, device, seed: int, momentum: float,
+                 weight_decay: float, eps: float = 1e-5, bn_momentum: float = 0.1):
+        C, H, W = shape
+        k, s, p = pool
+        if H + 2 * p < k or W + 2 * p < k:
+            raise ValueError(f"LINEAR_EVAL.POOLS.{tap}: the window {k} is larger than the padded {H}x{W} activation")
+        self.tap, self.pool, self.C = tap, (k, s, p), C
+        self.OH, self.OW = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        self.dim, self.eps, self.bn_momentum = C * self.OH * self.OW, eps, bn_momentum
+        self.probe = LinearProbe(num_classes, self.dim, device, seed, momentum, weight_decay)
+        self.gamma = torch.ones(C, device=device).requires_grad_(True)
+        self.beta = torch.zeros(C, device=device).requires_grad_(True)
+        self.gamma.grad, self.beta.grad = torch.zeros_like(self.gamma), torch.zeros_like(self.beta)
+        self.running_mean, self.running_var = torch.zeros(C, device=device), torch.ones(C, device=device)
+        # the head's one SGD; no weight decay on the BatchNorm (the reference's regularize_bn: False)
+        self.probe.opt.add_param_group({"params": [self.gamma, self.beta], "weight_decay": 0.0})
+
+    def features(self, x: torch.Tensor, train: bool) -> torch.Tensor:
+        """[N, dim] bf16: the Linear's input rows in (oh, ow, c) order, a view of the BatchNorm's output."""
+        if train:
+            f = _PoolBN.apply(x, self.gamma, self.beta, self.running_mean, self.running_var, self.pool, self.eps,
+                              self.bn_momentum)
+        else:
+            y = ops.avgpool_bn_stats(x, *self.pool)[0]
+            f = ops.OPS.bn_eval_f32(y, self.gamma.detach(), self.beta.detach(), self.running_mean, self.running_var,
+                                    self.eps)
+        return f.permute(0, 2, 3, 1).reshape(f.shape[0], self.dim)
+
+    def train_step(self, x: torch.Tensor, labels: torch.Tensor, lr: float) -> torch.Tensor:
+        p = self.probe
+        for g in (p.weight.grad, p.bias.grad, self.gamma.grad, self.beta.grad):
+            g.zero_()
+        y = ops.linear(self.features(x, True), p.weight.detach().to(torch.bfloat16), p.bias.detach(), p.weight.grad,
+                       p.bias.grad)
+        loss = ops.cross_entropy(y[:, :p.num_classes], labels)
+        loss.backward()
+        for gp in p.opt.param_groups:
+            gp["lr"] = lr
+        p.opt.step()
+        return loss.detach()
+
+    @torch.no_grad()
+    def score(self, x: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+        return self.probe.score(self.features(x, False), labels)
+
+    def _nchw(self, w: torch.Tensor) -> torch.Tensor:  # [n, (oh, ow, c)] -> [n, (c, oh, ow)]
+        return w.reshape(-1, self.OH, self.OW, self.C).permute(0, 3, 1, 2).reshape(w.shape[0], self.dim)
+
+    def _nhwc(self, w: torch.Tensor) -> torch.Tensor:  # [n, (c, oh, ow)] -> [n, (oh, ow, c)]
+        return w.reshape(-1, self.C, self.OH, self.OW).permute(0, 2, 3, 1).reshape(w.shape[0], self.dim)
+
+    def state_dict(self) -> dict:
+        n = self.probe.num_classes
+        return {"weight": self._nchw(self.probe.weight.detach()[:n]).cpu().clone(),
+                "bias": self.probe.bias.detach()[:n].cpu().clone(),
+                "bn.weight": self.gamma.detach().cpu().clone(), "bn.bias": self.beta.detach().cpu().clone(),
+                "bn.running_mean": self.running_mean.cpu().clone(), "bn.running_var": self.running_var.cpu().clone()}
+
+    def load_state_dict(self, sd: dict) -> None:
+        n = self.probe.num_classes
+        if tuple(sd["weight"].shape) != (n, self.dim):
+            raise ValueError(f"linear evaluation: head {self.tap} holds a weight of shape {tuple(sd['weight'].shape)}, "
+                             f"the pools and image size here need {(n, self.dim)}")
+        with torch.no_grad():
+            self.probe.weight[:n].copy_(self._nhwc(sd["weight"]))
+            self.probe.bias[:n].copy_(sd["bias"])
+            for t, k in ((self.gamma, "bn.weight"), (self.beta, "bn.bias"), (self.running_mean, "bn.running_mean"),
+                         (self.running_var, "bn.running_var")):
+                t.copy_(sd[k])
+
+
+class EvalMLP:
+    """The five heads of ``LINEAR_EVAL.PROTOCOL=eval_mlp`` (the reference's
+    ``eval_resnet_8gpu_transfer_in1k_linear``), trained side by side on one frozen forward
+    (``FrozenTrunk.forward_features``): each its own Linear, BatchNorm and SGD.  In ``train_linear`` it
+    stands where the ``LinearProbe`` stands: ``train_step`` returns the five losses, ``score`` a
+    [5, 4] block, in ``taps`` order."""
+
+    taps = TAPS
+
+    def __init__(self, num_classes: int, size: int = 224, pools=None, device="cpu", seed: int = LINEAR_SEED,
+                 momentum: float = 0.9, weight_decay: float = 1e-6):
+        shapes, pools = tap_shapes(int(size)), resolve_pools(pools)
+        self.heads = [EvalMLPHead(t, shapes[t], pools[t], num_classes, device, int(seed) + i, momentum, weight_decay)
+                      for i, t in enumerate(self.taps)]
+
+    def train_step(self, feats: Dict[str, torch.Tensor], labels: torch.Tensor, lr: float) -> torch.Tensor:
+        return torch.stack([h.train_step(feats[h.tap], labels, lr) for h in self.heads])
+
+    @torch.no_grad()
+    def score(self, feats: Dict[str, torch.Tensor], labels: torch.Tensor) -> torch.Tensor:
+        return torch.stack([h.score(feats[h.tap], labels) for h in self.heads])
+
+    def state_dict(self) -> dict:
+        return {"protocol": "eval_mlp", "heads": {h.tap: h.state_dict() for h in self.heads}}
+
+    def load_state_dict(self, sd: dict) -> None:
+        _check_protocol(sd, "eval_mlp")
+        for h in self.heads:
+            h.load_state_dict(sd["heads"][h.tap])
+
 
 def train_linear(extract: Callable[[torch.Tensor], torch.Tensor], train_stream, test_stream, num_classes: int,
                  settings: Optional[dict] = None, device="cpu", metrics_file: Optional[str] = None,
@@ -122,6 +314,8 @@ def train_linear(extract: Callable[[torch.Tensor], torch.Tensor], train_stream, 
     if probe is None:
         probe = LinearProbe(num_classes, device=device, seed=int(s["SEED"]), momentum=float(s["MOMENTUM"]),
                             weight_decay=float(s["WEIGHT_DECAY"]))
+    if s.get("LOAD_HEADS"):
+        load_heads(str(s["LOAD_HEADS"]), probe)
     records, step = [], 0
     for e in range(epochs):
         loss_sum = None
@@ -138,18 +332,30 @@ def train_linear(extract: Callable[[torch.Tensor], torch.Tensor], train_stream, 
             total = vec if total is None else total + vec
         if total is None or loss_sum is None:
             raise ValueError("linear evaluation: a stream served no image")
-        # the evaluation's only device-to-host copy (the epoch's summed train loss rides along)
-        ls, n, top1, top5, tl = torch.cat([total, loss_sum.reshape(1)]).cpu().tolist()
+        # the evaluation's only device-to-host copy (the epoch's summed train loss rides along); one
+        # row per head, the last one (the only one, or res5's) under the unsuffixed keys
+        taps = getattr(probe, "taps", None)
+        flat = torch.cat([total.reshape(-1), loss_sum.reshape(-1)]).cpu().tolist()
+        nh = len(flat) // 5
+        ls, n, top1, top5 = flat[4 * (nh - 1):4 * nh]
+        tl = flat[-1]
         rec = {"linear_top1": top1 / max(n, 1.0), "linear_top5": top5 / max(n, 1.0), "linear_loss": ls / max(n, 1.0),
                "linear_epoch": e + 1, "linear_train_images": len(train_stream), "linear_test_images": int(n),
                "linear_classes": int(num_classes), "linear_train_loss": tl / max(spe, 1),
                "eval": True, **(extra or {})}
+        for i, tap in enumerate(taps or ()):
+            hl, hn, h1, h5 = flat[4 * i:4 * i + 4]
+            rec.update({f"linear_top1_{tap}": h1 / max(hn, 1.0), f"linear_top5_{tap}": h5 / max(hn, 1.0),
+                        f"linear_loss_{tap}": hl / max(hn, 1.0),
+                        f"linear_train_loss_{tap}": flat[4 * nh + i] / max(spe, 1)})
         records.append(rec)
         if metrics_file:
             with open(metrics_file, "a") as f:
                 f.write(json.dumps(rec) + "\n")
         logger.info(f"linear evaluation epoch {e + 1}/{epochs}: top-1 {rec['linear_top1']:.4f} top-5 "
                     f"{rec['linear_top5']:.4f} test loss {rec['linear_loss']:.4f} ({rec['linear_test_images']} images)")
+    if s.get("SAVE_HEADS"):
+        save_heads(str(s["SAVE_HEADS"]), probe)
     return records
 
 
@@ -201,8 +407,16 @@ def linear_evaluate(model, sets: dict, device, metrics_file: Optional[str] = Non
     test = ImageFolderEvalStream(sets["test"], B, device, indices=sets["test_indices"], size=int(s["CENTER_CROP"]),
                                  resize=int(s["RESIZE"]), num_workers=sets["num_workers"])
     test.labels = sets["test_labels"][sets["test_indices"]]
+    extract, probe = trunk, None
+    if protocol(s) == "eval_mlp":
+        if int(s["CROP_SIZE"]) != int(s["CENTER_CROP"]):
+            raise ValueError("LINEAR_EVAL.PROTOCOL=eval_mlp: CROP_SIZE and CENTER_CROP must agree (the heads' input "
+                             f"widths follow the image size), got {s['CROP_SIZE']} and {s['CENTER_CROP']}")
+        probe = EvalMLP(sets["num_classes"], int(s["CROP_SIZE"]), s.get("POOLS"), device, seed=int(s["SEED"]),
+                        momentum=float(s["MOMENTUM"]), weight_decay=float(s["WEIGHT_DECAY"]))
+        extract = trunk.forward_features
     try:
-        return train_linear(trunk, train, test, sets["num_classes"], s, device, metrics_file, extra)
+        return train_linear(extract, train, test, sets["num_classes"], s, device, metrics_file, extra, probe)
     finally:
         train.close()
         test.close()
