@@ -7,7 +7,14 @@ inputs, at the headline micro-batch's M = 39424 target rows and V = 30000.
 The arms alternate call by call inside each round (device events around one forward + backward,
 cold MALL, median of --iters after a warm-up of every arm); one JSON line per round with the time
 per call and ``max_memory_allocated`` of each arm above the bytes held before it ran, appended to
---out (default profiles/mlm_xent.jsonl)."""
+--out (default profiles/mlm_xent.jsonl).
+
+    python bench/mlm_head_bench.py --eval [--M 32768] ...
+
+times the evaluation instead, forward only: ops.mlm_eval_cross_entropy against the decoder GEMM
+(ops.linear) + ops.eval_cross_entropy that evaluate_batch ran before it, at the evaluation batch's
+M = 64 x 512 rows (--M 4928 for 64 x 77); the same record with each arm's loss sum and top-1 / top-5
+counts, appended to profiles/mlm_eval.jsonl."""
 import argparse
 import json
 import os
@@ -21,12 +28,15 @@ sys.path.insert(0, ROOT)
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--M", type=int, default=39424)
+    ap.add_argument("--eval", action="store_true", help="the evaluation arms (forward only)")
+    ap.add_argument("--M", type=int, default=None, help="rows (default 39424; --eval: 32768)")
     ap.add_argument("--V", type=int, default=30000)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mlm_xent.jsonl"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    args.M = args.M or (32768 if args.eval else 39424)
+    args.out = args.out or os.path.join(ROOT, "profiles", "mlm_eval.jsonl" if args.eval else "mlm_xent.jsonl")
     if not torch.cuda.is_available():
         raise SystemExit("mlm_head_bench needs a GPU")
     import dedloc_amd.ops as ops
@@ -47,9 +57,21 @@ def main():
     def composed():
         return ops.cross_entropy(ops.linear(t, w, bias, gw, gb), labels)
 
-    arms = {"fused": fused, "composed": composed}
+    def fused_eval():
+        return ops.mlm_eval_cross_entropy(t, w, bias, labels)
+
+    def composed_eval():
+        return ops.eval_cross_entropy(ops.linear(t, w, bias), labels)
+
+    arms = {"fused": fused_eval, "composed": composed_eval} if args.eval else {"fused": fused, "composed": composed}
+    stats = {}
 
     def call(fn):
+        if args.eval:
+            with torch.no_grad():
+                out = fn()
+            stats[fn] = {k: v for k, v in out.items() if k != "loss_sum"}
+            return out["loss_sum"]
         t.grad = None
         loss = fn()
         loss.backward()
@@ -65,6 +87,7 @@ def main():
         torch.cuda.synchronize()
         peak[name] = torch.cuda.max_memory_allocated() - base
         peak[name + "_loss"] = float(loss)
+        peak[name + "_stats"] = {k: int(v) for k, v in stats.get(fn, {}).items()}
         del loss
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     for rnd in range(args.rounds):
@@ -78,13 +101,14 @@ def main():
                 b.record()
                 evs[name].append((a, b))
         torch.cuda.synchronize()
-        rec = {"bench": "mlm_head", "M": M, "V": V, "round": rnd, "iters": args.iters,
+        rec = {"bench": "mlm_eval" if args.eval else "mlm_head", "M": M, "V": V, "round": rnd, "iters": args.iters,
                "logits_bytes": M * V * 2}
         for name in arms:
             ts = sorted(a.elapsed_time(b) * 1e3 for a, b in evs[name])
             rec[name + "_us"] = round(ts[len(ts) // 2], 1)
             rec[name + "_peak_bytes"] = peak[name]
             rec[name + "_loss"] = peak[name + "_loss"]
+            rec.update({f"{name}_{k}": v for k, v in peak[name + "_stats"].items()})
         rec["peak_drop_bytes"] = peak["composed"] - peak["fused"]
         print(json.dumps(rec), flush=True)
         with open(args.out, "a") as f:

@@ -428,9 +428,11 @@ std::tuple<at::Tensor, at::Tensor> xent_eval(const at::Tensor& logits, const at:
 
 // ------------------------------------------------------------------ fused MLM head (mlm_xent.hip)
 // The operands both directions share: t [M, 128] and w [V, 128] bf16 with unit column stride, bias
-// [V] bf16 or fp32, labels int64 [M]; the bias scratch comes from the caching allocator.
+// [V] bf16 or fp32, labels int64 [M]; the bias scratch (`bias_copies` padded arrays of V floats)
+// comes from the caching allocator.
 inline DlMlmXent mlm_xent_desc(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias,
-                               const at::Tensor& labels, int64_t ignore_index, at::Tensor& bias_ws, const char* what) {
+                               const at::Tensor& labels, int64_t ignore_index, at::Tensor& bias_ws, const char* what,
+                               int bias_copies = 1) {
   for (const at::Tensor* x : {&t, &w})
     TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 && x->dim() == 2 && x->stride(1) == 1, what,
                 ": t and w must be 2-D bf16 GPU tensors with unit column stride");
@@ -447,7 +449,7 @@ inline DlMlmXent mlm_xent_desc(const at::Tensor& t, const at::Tensor& w, const a
   a.bias = bias.data_ptr(), a.bias_bf16 = bias.scalar_type() == at::kBFloat16;
   a.labels = labels.data_ptr<long>(), a.ignore_index = (int)ignore_index;
   a.M = (int)t.size(0), a.V = (int)w.size(0), a.E = (int)t.size(1);
-  bias_ws = at::empty({(a.V + 63) / 64 * 64}, t.options().dtype(at::kFloat));
+  bias_ws = at::empty({(int64_t)bias_copies * ((a.V + 63) / 64 * 64)}, t.options().dtype(at::kFloat));
   a.bias_ws = f32(bias_ws);
   return a;
 }
@@ -485,6 +487,18 @@ at::Tensor mlm_xent_bwd(const at::Tensor& t, const at::Tensor& w, const at::Tens
   a.dt = bf(dt), a.lddt = a.E;
   check(dl_mlm_xent_bwd(a, cur_stream(t)), "mlm_xent_bwd");
   return dt;
+}
+
+// per row: the loss (natural log) and the label's rank among the fp32 scores, ties to the lower index
+std::tuple<at::Tensor, at::Tensor> mlm_xent_eval(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias,
+                                                 const at::Tensor& labels, int64_t ignore_index) {
+  at::Tensor bias_ws;
+  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, bias_ws, "mlm_xent_eval", 2);
+  auto row_loss = at::empty({a.M}, t.options().dtype(at::kFloat));
+  auto row_rank = at::empty({a.M}, t.options().dtype(at::kInt));
+  a.row_loss = f32(row_loss), a.row_rank = row_rank.data_ptr<int>();
+  check(dl_mlm_xent_eval(a, cur_stream(t)), "mlm_xent_eval");
+  return {row_loss, row_rank};
 }
 
 // ------------------------------------------------------------------ kNN evaluation (knn.hip)
@@ -2150,6 +2164,7 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("xent_eval", &xent_eval);
   m.impl("mlm_xent_fwd", &mlm_xent_fwd);
   m.impl("mlm_xent_bwd", &mlm_xent_bwd);
+  m.impl("mlm_xent_eval", &mlm_xent_eval);
   m.impl("knn_topk", &knn_topk);
   m.impl("knn_vote", &knn_vote);
   m.impl("attn_fwd", &attn_fwd);

@@ -204,7 +204,7 @@ struct DlMlmXent {
   const void* bias = nullptr; int bias_bf16 = 0;  // [V], bf16 or fp32
   const long* labels = nullptr; int ignore_index = -100;  // [M]
   int M = 0, V = 0, E = 0;  // E must be 128; rows of t, w, dt 16-byte aligned
-  float* bias_ws = nullptr;  // scratch: V rounded up to 64 floats
+  float* bias_ws = nullptr;  // scratch: V rounded up to 64 floats (evaluation: twice that)
   float* lse = nullptr;      // [M] log2 units: written by the forward, read by the backward
   // forward: per-row loss [M] (scratch) and the mean over the live rows (0 without one)
   float* row_loss = nullptr; float* loss = nullptr;
@@ -212,8 +212,13 @@ struct DlMlmXent {
   // dt [M, E] bf16; gw [V, E] / gb [V] fp32, dense, ADDED into (both or neither)
   const float* gloss = nullptr; float* row_ws = nullptr;
   bf16_t* dt = nullptr; long lddt = 0; float* gw = nullptr; float* gb = nullptr;
+  // evaluation: writes row_loss [M] (natural log; 0 on an ignored row) and row_rank [M], the number
+  // of columns j with s_j > s_label, or s_j == s_label and j < label, on the fp32 scores (-1 on an
+  // ignored row); reads neither lse nor loss
+  int* row_rank = nullptr;
 };
 int dl_mlm_xent_fwd(const DlMlmXent& a, hipStream_t st);
+int dl_mlm_xent_eval(const DlMlmXent& a, hipStream_t st);
 int dl_mlm_xent_bwd(const DlMlmXent& a, hipStream_t st);
 
 // swav.hip

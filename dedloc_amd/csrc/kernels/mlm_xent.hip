@@ -14,6 +14,8 @@
 //          output accumulator, and every w fragment read from LDS then feeds two MFMAs.  Running
 //          max / sum per lane, halves combined by v_permlane32_swap, the target logit picked up in
 //          the tile that holds the label.  Writes lse (log2 units) and the per-row loss.
+//   eval   the forward's split swept twice in one launch, forward only: per-row loss and the
+//          label's rank among the fp32 scores (see the kernel).  One or two sub-blocks per wave.
 //   bwd dt token on the lane, one sub-block per wave: t 32 + dt 64 + scores 32 registers.
 //          P = exp2(s + bias - lse) is recomputed, dS = (P - onehot) g / count is packed to bf16
 //          and dt += dS W accumulates from transposed reads of the same w tiles.
@@ -40,6 +42,7 @@ constexpr int NBUF = 2;                           // ring slots
 constexpr int W_STAGE = 2 * TILE_BYTES + 256;     // fwd, dt: [w dims 0-63 | w dims 64-127 | 64 bias]
 constexpr int T_STAGE = 2 * TILE_BYTES + 768;     // dw: [t dims 0-63 | t dims 64-127 | lse | scale | label]
 constexpr int FWD_ROWS = 256, DT_ROWS = 128, DW_ROWS = 64;  // rows a workgroup owns
+constexpr int EVAL_SMALL_M = 256 * 256;  // eval: up to here 256-row blocks are fewer than the 256 compute units
 
 // dma_tile with the source row clamped to n - 1 (the last tile of a tail re-reads the last row)
 __device__ __forceinline__ void dma_tile_clamp(const bf16_t* g, long ld, int row0, int n, uint8_t* tile, int w,
@@ -92,13 +95,23 @@ __device__ __forceinline__ void zero(floatx16& x) {
 __device__ __forceinline__ void ring_wait() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // ---------------------------------------------------------------------------------- preparation
-// out[i] = bias[i] * log2(e) for i < V, -1e30 up to the next multiple of 64
+// out[i] = bias[i] * log2(e) for i < V, -1e30 up to the next multiple of 64; NATURAL: a second
+// array out[Vp + i] = bias[i] with the same padding (the evaluation's rank sweep compares in the
+// logits' own units)
+template <bool NATURAL = false>
 __global__ void mlm_bias_kernel(const void* __restrict__ bias, int bias_bf16, float* __restrict__ out, int V, int Vp) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= Vp) return;
-  float b = NEG_BIG;
-  if (i < V) b = (bias_bf16 ? bf2f(static_cast<const bf16_t*>(bias)[i]) : static_cast<const float*>(bias)[i]) * LOG2E;
-  out[i] = b;
+  if constexpr (NATURAL) {
+    const float b = i < V ? (bias_bf16 ? bf2f(static_cast<const bf16_t*>(bias)[i]) : static_cast<const float*>(bias)[i])
+                          : NEG_BIG;
+    out[i] = i < V ? b * LOG2E : NEG_BIG;
+    out[Vp + i] = b;
+  } else {
+    float b = NEG_BIG;
+    if (i < V) b = (bias_bf16 ? bf2f(static_cast<const bf16_t*>(bias)[i]) : static_cast<const float*>(bias)[i]) * LOG2E;
+    out[i] = b;
+  }
 }
 
 __device__ __forceinline__ float live_rows(const long* __restrict__ labels, int M, int ignore_index, float* scratch) {
@@ -227,6 +240,192 @@ __global__ __launch_bounds__(256, 2) void mlm_xent_fwd_kernel(const bf16_t* __re
     if (row < M && hh == 0) {
       lse[row] = l2;
       row_loss[row] = lab[u] >= 0 ? (l2 - target) * LN2 : 0.f;
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------ eval
+// The forward's split (token on the lane, U sub-blocks per wave, 128 U rows per workgroup) swept
+// twice over the vocabulary in one launch.  Sweep 1 is the forward with one difference: the label's
+// RAW accumulator is picked up, so that afterwards both its log2 score (for the loss, the forward's
+// arithmetic) and its natural score sy = acc + bias (for the rank) follow from it.  Sweep 2 restarts
+// the ring at vocabulary row 0, now staging the natural bias, with the t fragments still in
+// registers, and counts per lane the columns that beat the label: s_j > sy, or s_j == sy and j < y.
+// The recomputed accumulators carry the bits sweep 1 saw, so ties are exact.
+//
+// Per score the count is one add, one compare and one add-with-carry-in: the tie rule is folded
+// into the threshold.  In a tile that lies wholly below the label's column every tie counts, and
+// s >= sy is s > lo with lo the next float below sy (fp32 denormals are not flushed in this file's
+// kernels: .amdhsa_float_denorm_mode_32 3); in a tile wholly above it the threshold is sy.  Each lane
+// selects its own once per tile; only the tile that holds a label of the wave selects per column.
+// The vocabulary tail's -1e30 bias keeps its columns below every threshold.
+
+// the largest float below x (x finite)
+__device__ __forceinline__ float next_below(float x) {
+  const uint32_t b = __float_as_uint(x);
+  return __uint_as_float(x > 0.f ? b - 1u : (x < 0.f ? b + 1u : 0x80000001u));
+}
+__device__ __forceinline__ int half_sum_int(int x) {
+  const auto r = __builtin_amdgcn_permlane32_swap((uint32_t)x, (uint32_t)x, false, false);
+  return (int)(r[0] + r[1]);
+}
+// raw scores of the staged 64 vocabulary rows against this wave's U t sub-blocks
+template <int U>
+__device__ __forceinline__ void tile_scores(const uint8_t* Ws, const bf16x8 (&tf)[U][8], int r, int hh,
+                                            floatx16 (&s)[U][2]) {
+#pragma unroll
+  for (int u = 0; u < U; ++u)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) zero(s[u][j]);
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) {
+      const bf16x8 a = block_row_frag(Ws, 32 * j + r, ks, hh);
+#pragma unroll
+      for (int u = 0; u < U; ++u) s[u][j] = mfma32(a, tf[u][ks], s[u][j]);
+    }
+}
+
+// bias2 = [log2-unit bias | natural bias], Vp floats each.  row_loss 0 / row_rank -1 on an ignored
+// row; a label outside [0, V) that is not ignore_index is never used as an index: (NaN, -1).
+template <int U>
+__global__ __launch_bounds__(256, 2) void mlm_xent_eval_kernel(const bf16_t* __restrict__ t, long ldt,
+                                                                const bf16_t* __restrict__ w, long ldw,
+                                                                const float* __restrict__ bias2, int Vp,
+                                                                const long* __restrict__ labels,
+                                                                float* __restrict__ row_loss, int* __restrict__ row_rank,
+                                                                int M, int V, int ignore_index) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * W_STAGE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int nt = (V + 63) / 64;
+  auto issue = [&](int vt, const float* bias) {  // vocabulary tile vt -> slot vt % NBUF
+    uint8_t* slot = smem + (vt % NBUF) * W_STAGE;
+    dma_block(w, ldw, vt * 64, V, slot, wv, lane);
+    dma_f32x64(bias + vt * 64, slot + 2 * TILE_BYTES, lane);
+  };
+  issue(0, bias2);
+
+  const int row0 = blockIdx.x * (128 * U) + wv * (32 * U) + r;
+  bf16x8 tf[U][8];
+  int lab[U];
+  bool bad[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int row = row0 + 32 * u;
+    const int rc = min(row, M - 1);
+    load_row_frags(t, ldt, rc, hh, tf[u]);
+    const long l = labels[rc];
+    const bool in = l >= 0 && l < V;
+    lab[u] = (row < M && l != ignore_index && in) ? (int)l : -1;
+    bad[u] = l != ignore_index && !in;
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    settle(lab[u]);
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks) settle(tf[u][ks]);
+  }
+  float m[U], l[U], xa[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) m[u] = NEG_BIG, l[u] = 0.f, xa[u] = 0.f;
+
+  // ---- sweep 1: running max / sum and the label's raw accumulator
+  wait_vm_all();
+  for (int vt = 0; vt < nt; ++vt) {
+    ring_wait();
+    __syncthreads();
+    if (vt + 1 < nt) issue(vt + 1, bias2);
+    const uint8_t* Ws = smem + (vt % NBUF) * W_STAGE;
+    const float* bs = reinterpret_cast<const float*>(Ws + 2 * TILE_BYTES);
+    floatx16 s[U][2];
+    tile_scores<U>(Ws, tf, r, hh, s);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int d = lab[u] - vt * 64;  // the label's row in this tile
+      if (__ballot((unsigned)d < 64u) != 0) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 16; ++i)
+            if (32 * j + crow(i, hh) == d) xa[u] = s[u][j][i];
+      }
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) s[u][j][i] = fmaf(s[u][j][i], LOG2E, bs[32 * j + crow(i, hh)]);
+      const float mx = half_max(vmax3(max16(s[u][0]), max16(s[u][1]), m[u]));
+      const float nm = -mx;
+      float rsa[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) rsa[i & 3] += __builtin_amdgcn_exp2f(s[u][j][i] + nm);
+      l[u] = fmaf(l[u], __builtin_amdgcn_exp2f(m[u] + nm), half_sum((rsa[0] + rsa[1]) + (rsa[2] + rsa[3])));
+      m[u] = mx;
+    }
+  }
+
+  // ---- between the sweeps: both halves of a row learn the label's scores
+  float loss[U], sy[U], lo[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const float acc = half_sum(xa[u]);  // one half found it, the other holds 0
+    const int li = max(lab[u], 0);
+    const float l2 = m[u] + log2f(l[u]);
+    loss[u] = lab[u] >= 0 ? (l2 - fmaf(acc, LOG2E, bias2[li])) * LN2 : (bad[u] ? __builtin_nanf("") : 0.f);
+    sy[u] = acc + bias2[Vp + li];
+    lo[u] = next_below(sy[u]);
+    settle(loss[u]);
+    settle(sy[u]);
+    settle(lo[u]);
+  }
+  wait_vm_all();
+  __syncthreads();  // every wave is done with sweep 1's last slot before tile 0 lands on slot 0 again
+  const float* biasn = bias2 + Vp;
+  issue(0, biasn);
+
+  // ---- sweep 2: count the columns that beat the label
+  int cnt[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) cnt[u] = 0;
+  for (int vt = 0; vt < nt; ++vt) {
+    ring_wait();
+    __syncthreads();
+    if (vt + 1 < nt) issue(vt + 1, biasn);
+    const uint8_t* Ws = smem + (vt % NBUF) * W_STAGE;
+    const float* bs = reinterpret_cast<const float*>(Ws + 2 * TILE_BYTES);
+    floatx16 s[U][2];
+    tile_scores<U>(Ws, tf, r, hh, s);
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int d = lab[u] - vt * 64;
+      int c4[4] = {0, 0, 0, 0};
+      if (__ballot((unsigned)d < 64u) == 0) {  // no label of this wave's rows in the tile
+        const float thr = d >= 64 ? lo[u] : sy[u];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) c4[i & 3] += s[u][j][i] + bs[32 * j + crow(i, hh)] > thr ? 1 : 0;
+      } else {
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) {
+            const int col = 32 * j + crow(i, hh);
+            c4[i & 3] += s[u][j][i] + bs[col] > (col < d ? lo[u] : sy[u]) ? 1 : 0;
+          }
+      }
+      cnt[u] += (c4[0] + c4[1]) + (c4[2] + c4[3]);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int row = row0 + 32 * u;
+    const int rank = half_sum_int(cnt[u]);
+    if (row < M && hh == 0) {
+      row_loss[row] = loss[u];
+      row_rank[row] = lab[u] >= 0 ? rank : -1;
     }
   }
 }
@@ -420,7 +619,7 @@ static bool mlm_xent_ok(const DlMlmXent& a) {
 
 static void mlm_bias(const DlMlmXent& a, hipStream_t st) {
   const int Vp = (a.V + 63) / 64 * 64;
-  mlm_bias_kernel<<<(Vp + 255) / 256, 256, 0, st>>>(a.bias, a.bias_bf16, a.bias_ws, a.V, Vp);
+  mlm_bias_kernel<><<<(Vp + 255) / 256, 256, 0, st>>>(a.bias, a.bias_bf16, a.bias_ws, a.V, Vp);
 }
 
 int dl_mlm_xent_fwd(const DlMlmXent& a, hipStream_t st) {
@@ -431,6 +630,23 @@ int dl_mlm_xent_fwd(const DlMlmXent& a, hipStream_t st) {
                                                                          a.lse, a.row_loss, a.M, a.V, a.ignore_index);
   }
   mlm_loss_kernel<<<1, 1024, 0, st>>>(a.row_loss, a.labels, a.M, a.ignore_index, a.loss);
+  return 0;
+}
+
+int dl_mlm_xent_eval(const DlMlmXent& a, hipStream_t st) {
+  if (!mlm_xent_ok(a)) return -1;
+  if (a.M == 0) return 0;
+  const int Vp = (a.V + 63) / 64 * 64;
+  mlm_bias_kernel<true><<<(Vp + 255) / 256, 256, 0, st>>>(a.bias, a.bias_bf16, a.bias_ws, a.V, Vp);
+  // A workgroup walks the whole vocabulary twice, so the call takes as long as one workgroup does:
+  // while 256-row blocks would leave compute units idle, 128-row blocks (one sub-block per wave)
+  // halve the work per tile and double the workgroups
+  if (a.M <= EVAL_SMALL_M)
+    mlm_xent_eval_kernel<1><<<(a.M + 127) / 128, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, Vp, a.labels, a.row_loss,
+                                                              a.row_rank, a.M, a.V, a.ignore_index);
+  else
+    mlm_xent_eval_kernel<2><<<(a.M + 255) / 256, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, Vp, a.labels, a.row_loss,
+                                                              a.row_rank, a.M, a.V, a.ignore_index);
   return 0;
 }
 

@@ -153,8 +153,12 @@ _SHARED_WGRAD = True
 _LAST_LAYER_ROWS = True
 # AlbertForPreTraining's MLM loss on ops.mlm_cross_entropy: the tied decoder GEMM and the
 # cross-entropy in one set of kernels that keep the logits fp32 and never store them.  Embedding
-# size 128 only; a call that asks for the logits (return_logits) and evaluate_batch keep the decoder GEMM.
+# size 128 only; a call that asks for the logits (return_logits) keeps the decoder GEMM.
 _FUSED_MLM_LOSS = True
+# evaluate_batch's MLM statistics on ops.mlm_eval_cross_entropy: loss and label rank from the same
+# fp32 scores, again without the logits.  Embedding size 128 on the GPU; anything else goes through
+# the decoder GEMM and ops.eval_cross_entropy.
+_FUSED_MLM_EVAL = True
 
 
 class _AlbertLayerFn(torch.autograd.Function):
@@ -778,7 +782,8 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
     def evaluate_batch(self, batch, lengths=None):
         """Held-out statistics of one batch (a stream's ``next_batch()`` dict), forward only: eval mode
         and ``no_grad`` (the previous mode is restored), the encoder and head path of ``forward``
-        (``pack_sequences`` and both MLM target forms included) ending in ``ops.eval_cross_entropy``.
+        (``pack_sequences`` and both MLM target forms included) ending in ``ops.eval_cross_entropy``
+        (the MLM head, under ``_FUSED_MLM_EVAL``: ``ops.mlm_eval_cross_entropy``, without the [M, V] logits).
         No gradient buffer is written, no [M, V] gradient is made and no random generator is drawn
         from.  Returns device scalars: ``mlm_loss_sum``, ``mlm_count``, ``mlm_top1``, ``mlm_top5``,
         ``sop_loss_sum``, ``sop_count``, ``sop_correct`` (sums and counts, so batches add up)."""
@@ -794,7 +799,11 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
                 rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, pos, batch.get("mlm_labels"), sel)
                 if rows is None:
                     raise ValueError("evaluate_batch needs MLM targets: labels or mlm_positions/mlm_labels")
-                mlm = ops.eval_cross_entropy(self._mlm_logits(h, rows), tgt, topk=(1, 5))
+                if _FUSED_MLM_EVAL and self.config.embedding_size == 128 and h.is_cuda:
+                    w, b, _, _ = self._mlm_decoder()
+                    mlm = ops.mlm_eval_cross_entropy(self._mlm_transform(h, rows), w, b, tgt, topk=(1, 5))
+                else:
+                    mlm = ops.eval_cross_entropy(self._mlm_logits(h, rows), tgt, topk=(1, 5))
                 sop = ops.eval_cross_entropy(self._sop_logits(h, B, Sp, pk, row0), batch["sentence_order_label"],
                                              topk=(1,))
         finally:

@@ -367,12 +367,30 @@ def eval_cross_entropy(logits, labels, ignore_index=-100, topk=(1, 5)):
     reduced by plain ``sum`` — a fixed order, so two calls agree bitwise — and nothing is read back."""
     if not (logits.dim() == 2 and logits.stride(1) == 1 and logits.stride(0) >= logits.shape[1]):
         logits = logits.contiguous()
-    row_loss, row_rank = OPS.xent_eval(logits, labels.reshape(-1).contiguous(), ignore_index)
+    return _eval_sums(*OPS.xent_eval(logits, labels.reshape(-1).contiguous(), ignore_index), topk)
+
+
+def _eval_sums(row_loss, row_rank, topk):
     valid = row_rank >= 0
     out = {"loss_sum": row_loss.sum(dtype=torch.float64), "count": valid.sum()}
     for k in topk:
         out[f"top{k}"] = (valid & (row_rank < k)).sum()
     return out
+
+
+@torch.no_grad()
+def mlm_eval_cross_entropy(t, w, bias, labels, ignore_index=-100, topk=(1, 5)):
+    """``eval_cross_entropy(linear(t, w, bias), labels)`` for the tied MLM decoder without the [M, V]
+    logits (the ``mlm_xent_eval`` kernel: two sweeps over the vocabulary in one launch, the loss from
+    the first and the label's rank from the second).  t [M, 128] bf16 with unit column stride (a
+    strided row view is read in place), w [V, 128] bf16, bias [V].  The scores stay fp32, so the
+    ranks are those of the unrounded logits.  Returns what ``eval_cross_entropy`` returns."""
+    if t.dim() != 2 or w.dim() != 2 or t.shape[1] != 128 or w.shape[1] != 128:
+        raise ValueError(f"mlm_eval_cross_entropy needs an embedding size of 128, got t {tuple(t.shape)}, "
+                         f"w {tuple(w.shape)}")
+    if t.stride(1) != 1:
+        t = t.contiguous()
+    return _eval_sums(*OPS.mlm_xent_eval(t, w, bias.contiguous(), labels.reshape(-1).contiguous(), ignore_index), topk)
 
 
 @torch.no_grad()
@@ -416,7 +434,7 @@ def avgpool_bn_stats(x, k, stride, pad=0):
 
 __all__ = [
     "linear", "gelu_new", "tanh", "add_layernorm", "attention", "embed_layernorm", "cross_entropy",
-    "eval_cross_entropy", "knn_topk", "knn_classify", "avgpool_bn_stats", "OPS",
+    "eval_cross_entropy", "mlm_eval_cross_entropy", "knn_topk", "knn_classify", "avgpool_bn_stats", "OPS",
     "load_native", "native_loaded",
 ]
 

@@ -46,6 +46,7 @@ _SCHEMAS = [
     "mlm_xent_fwd(Tensor t, Tensor w, Tensor bias, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
     "mlm_xent_bwd(Tensor t, Tensor w, Tensor bias, Tensor labels, Tensor lse, Tensor gloss, Tensor(a!)? gw, "
     "Tensor(b!)? gb, int ignore_index) -> Tensor",
+    "mlm_xent_eval(Tensor t, Tensor w, Tensor bias, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
     "knn_topk(Tensor q, Tensor bank, int k, int splits=0) -> (Tensor, Tensor)",
     "knn_vote(Tensor vals, Tensor idx, Tensor bank_labels, Tensor targets, int num_classes, float sigma) "
     "-> (Tensor, Tensor)",
@@ -580,6 +581,15 @@ def _mlm_xent_bwd_cpu(t, w, bias, labels, lse, gloss, gw, gb, ignore_index):
     if gw is not None:
         gw.add_(ds.t() @ t.float())
     return _bf(ds @ w.float())
+
+
+@_impl("mlm_xent_eval")
+def _mlm_xent_eval_cpu(t, w, bias, labels, ignore_index):
+    """``xent_eval`` on logits = t w^T + bias kept in fp32 (never rounded to bf16): per row the loss
+    and the number of columns that beat the label, ties to the lower index; ignored rows are (0, -1)."""
+    if t.dim() != 2 or w.dim() != 2 or t.shape[1] != w.shape[1] or labels.numel() != t.shape[0]:
+        raise RuntimeError("mlm_xent_eval: t [M, E], w [V, E] and M labels")
+    return _xent_eval_cpu(t.float() @ w.float().t() + bias.float(), labels, ignore_index)
 
 
 @_impl("knn_topk")
