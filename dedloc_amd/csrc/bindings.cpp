@@ -1721,6 +1721,8 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
     return af ? affine_pass(y, *af) : y;
   }
   if (C % 64 == 0) {
+    // conv.hip's epilogue stores whole 8-channel chunks (16 bytes); nothing launches otherwise
+    TORCH_CHECK(K % 8 == 0, "conv2d_fwd: Cout must be a multiple of 8 (got ", K, ")");
     const DlConvGeom gm = geom(cbf(x), N, H, W, C, P, Q, stride, stride, R, S, -pad, 1, -pad, 1);
     if (af) {
       check(dl_conv_fwd_affine(gm, cbf(wk), R * S * C, (int)K, bf(y), (int)P, (int)Q, K, af->scale, af->shift, af->res,
@@ -1737,6 +1739,7 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
     return y;
   }
   if (stem_s2d_ok(C, R, S, stride, pad, H, W)) {
+    TORCH_CHECK(K % 8 == 0, "conv2d_fwd(stem): Cout must be a multiple of 8 (got ", K, ")");
     at::Tensor xs;
     if (cols.has_value()) {
       TORCH_CHECK(cols->scalar_type() == at::kBFloat16 && cols->is_contiguous() && cols->dim() == 2 &&

@@ -23,7 +23,8 @@
 // unconditional 16-byte buffer loads whose padding taps read zeros through the descriptor's range
 // check, so the compiler never branches around a load (§5 item 4(c)) and never waits early; two
 // register stage sets keep two k-tiles of loads in flight.  The forward kernel swaps the MFMA
-// operand roles so each lane owns 4 consecutive output channels of one pixel (8-byte NHWC stores).
+// operand roles so each lane owns 4 consecutive output channels of one pixel; the tile is staged
+// through LDS and leaves as 16-byte NHWC stores (8 channels), hence N % 8 and ldo % 8.
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -960,7 +961,9 @@ __global__ __launch_bounds__(256) void wt_transpose_kernel(const WtJobs P) {
 #endif
 int dl_conv_fwd_multi(const DlConvFwdJob* jobs, int njobs, int N, bf16_t* out, int OH, int OW, int osh, int osw,
                       long ldo, hipStream_t st, float* stats, const DlBnBwdEpi* bn) {
-  if (njobs < 1 || njobs > MAXJ || N % 4 || ldo % 4) return -1;
+  // the epilogue stores whole 8-channel chunks: a 4-channel tail would write into the next pixel
+  // (past the tensor at the last one)
+  if (njobs < 1 || njobs > MAXJ || N % 8 || ldo % 8) return -1;
   if (bn && (!stats || !bn->X || bn->ldx % 8 || (!bn->Y && (!bn->gamma || !bn->beta)))) return -1;
   // validate every job before anything launches (-1: nothing ran); all jobs must take one variant
   int variant = -1;
