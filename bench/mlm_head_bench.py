@@ -3,6 +3,7 @@
 inputs, at the headline micro-batch's M = 39424 target rows and V = 30000.
 
     python bench/mlm_head_bench.py [--M 39424] [--V 30000] [--rounds 3] [--iters 10] [--out FILE]
+                                   [--splits N ...]
 
 The arms alternate call by call inside each round (device events around one forward + backward,
 cold MALL, median of --iters after a warm-up of every arm); one JSON line per round with the time
@@ -14,8 +15,14 @@ per call and ``max_memory_allocated`` of each arm above the bytes held before it
 times the evaluation instead, forward only: ops.mlm_eval_cross_entropy against the decoder GEMM
 (ops.linear) + ops.eval_cross_entropy that evaluate_batch ran before it, at the evaluation batch's
 M = 64 x 512 rows (--M 4928 for 64 x 77); the same record with each arm's loss sum and top-1 / top-5
-counts, appended to profiles/mlm_eval.jsonl."""
+counts, appended to profiles/mlm_eval.jsonl.
+
+``fused`` is the launcher's own choice of vocabulary slices (``splits=0``).  --splits adds one arm
+``fused_s{n}`` per forced slice count to the same alternation: ``--splits 1`` is the unsplit kernels,
+a longer list is the sweep the launcher's rule in csrc/kernels/mlm_xent.hip is set from
+(profiles/mlm_head_split.jsonl)."""
 import argparse
+import functools
 import json
 import os
 import sys
@@ -34,6 +41,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--splits", type=int, nargs="*", default=[], help="forced vocabulary slice counts, one arm each")
     args = ap.parse_args()
     args.M = args.M or (32768 if args.eval else 39424)
     args.out = args.out or os.path.join(ROOT, "profiles", "mlm_eval.jsonl" if args.eval else "mlm_xent.jsonl")
@@ -51,19 +59,21 @@ def main():
     gb = torch.zeros(V, device="cuda")
     flush = torch.empty(512 << 20, dtype=torch.uint8, device="cuda")  # evicts the 256 MB MALL
 
-    def fused():
-        return ops.mlm_cross_entropy(t, w, bias, labels, gw, gb)
+    def fused(splits=0):
+        return ops.mlm_cross_entropy(t, w, bias, labels, gw, gb, splits=splits)
 
     def composed():
         return ops.cross_entropy(ops.linear(t, w, bias, gw, gb), labels)
 
-    def fused_eval():
-        return ops.mlm_eval_cross_entropy(t, w, bias, labels)
+    def fused_eval(splits=0):
+        return ops.mlm_eval_cross_entropy(t, w, bias, labels, splits=splits)
 
     def composed_eval():
         return ops.eval_cross_entropy(ops.linear(t, w, bias), labels)
 
     arms = {"fused": fused_eval, "composed": composed_eval} if args.eval else {"fused": fused, "composed": composed}
+    for n in args.splits:
+        arms[f"fused_s{n}"] = functools.partial(fused_eval if args.eval else fused, n)
     stats = {}
 
     def call(fn):

@@ -429,10 +429,10 @@ std::tuple<at::Tensor, at::Tensor> xent_eval(const at::Tensor& logits, const at:
 // ------------------------------------------------------------------ fused MLM head (mlm_xent.hip)
 // The operands both directions share: t [M, 128] and w [V, 128] bf16 with unit column stride, bias
 // [V] bf16 or fp32, labels int64 [M]; the bias scratch (`bias_copies` padded arrays of V floats)
-// comes from the caching allocator.
+// comes from the caching allocator.  `splits` (0: automatic) becomes the call's vocabulary slices.
 inline DlMlmXent mlm_xent_desc(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias,
-                               const at::Tensor& labels, int64_t ignore_index, at::Tensor& bias_ws, const char* what,
-                               int bias_copies = 1) {
+                               const at::Tensor& labels, int64_t ignore_index, int64_t splits, at::Tensor& bias_ws,
+                               const char* what, int bias_copies = 1) {
   for (const at::Tensor* x : {&t, &w})
     TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 && x->dim() == 2 && x->stride(1) == 1, what,
                 ": t and w must be 2-D bf16 GPU tensors with unit column stride");
@@ -451,13 +451,27 @@ inline DlMlmXent mlm_xent_desc(const at::Tensor& t, const at::Tensor& w, const a
   a.M = (int)t.size(0), a.V = (int)w.size(0), a.E = (int)t.size(1);
   bias_ws = at::empty({(int64_t)bias_copies * ((a.V + 63) / 64 * 64)}, t.options().dtype(at::kFloat));
   a.bias_ws = f32(bias_ws);
+  TORCH_CHECK(splits >= 0 && splits <= INT32_MAX, what, ": splits = ", splits, " must be 0 (automatic) or positive");
+  int cus = 0;
+  if (splits == 0)
+    TORCH_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t.get_device()) == hipSuccess, what,
+                ": cannot read the device's CU count");
+  a.splits = dl_mlm_xent_splits(a.M, a.V, (int)splits, cus);
   return a;
+}
+// scratch of `per_row` floats for each of M rounded up to 64 rows (a split call's partial results)
+inline at::Tensor mlm_xent_split_ws(const DlMlmXent& a, int64_t per_row, const at::Tensor& like, const char* what) {
+  const int64_t n = ((int64_t)a.M + 63) / 64 * 64 * per_row;
+  TORCH_CHECK(n * 4 <= ((int64_t)1 << 31), what, ": ", a.splits, " vocabulary slices of ", a.M,
+              " rows need a workspace of more than 2^31 bytes");
+  return at::empty({n}, like.options().dtype(at::kFloat));
 }
 
 std::tuple<at::Tensor, at::Tensor> mlm_xent_fwd(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias,
-                                                const at::Tensor& labels, int64_t ignore_index) {
-  at::Tensor bias_ws;
-  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, bias_ws, "mlm_xent_fwd");
+                                                const at::Tensor& labels, int64_t ignore_index, int64_t splits) {
+  at::Tensor bias_ws, part_ws;
+  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, splits, bias_ws, "mlm_xent_fwd");
+  if (a.splits > 1) a.part_ws = f32(part_ws = mlm_xent_split_ws(a, 3 * a.splits, t, "mlm_xent_fwd"));
   auto lse = at::empty({a.M}, t.options().dtype(at::kFloat));
   auto loss = at::empty({}, lse.options());
   auto row_loss = at::empty({a.M}, lse.options());
@@ -468,9 +482,10 @@ std::tuple<at::Tensor, at::Tensor> mlm_xent_fwd(const at::Tensor& t, const at::T
 
 at::Tensor mlm_xent_bwd(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias, const at::Tensor& labels,
                         const at::Tensor& lse, const at::Tensor& gloss, const c10::optional<at::Tensor>& gw,
-                        const c10::optional<at::Tensor>& gb, int64_t ignore_index) {
-  at::Tensor bias_ws;
-  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, bias_ws, "mlm_xent_bwd");
+                        const c10::optional<at::Tensor>& gb, int64_t ignore_index, int64_t splits) {
+  at::Tensor bias_ws, dt_ws;
+  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, splits, bias_ws, "mlm_xent_bwd");
+  if (a.splits > 1) a.dt_ws = f32(dt_ws = mlm_xent_split_ws(a, (int64_t)a.splits * a.E, t, "mlm_xent_bwd"));
   expect(lse, at::kFloat, "lse");
   expect(gloss, at::kFloat, "gloss");
   TORCH_CHECK(lse.numel() == a.M && gloss.numel() == 1, "mlm_xent_bwd: lse [M] and a scalar gloss");
@@ -491,9 +506,10 @@ at::Tensor mlm_xent_bwd(const at::Tensor& t, const at::Tensor& w, const at::Tens
 
 // per row: the loss (natural log) and the label's rank among the fp32 scores, ties to the lower index
 std::tuple<at::Tensor, at::Tensor> mlm_xent_eval(const at::Tensor& t, const at::Tensor& w, const at::Tensor& bias,
-                                                 const at::Tensor& labels, int64_t ignore_index) {
-  at::Tensor bias_ws;
-  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, bias_ws, "mlm_xent_eval", 2);
+                                                 const at::Tensor& labels, int64_t ignore_index, int64_t splits) {
+  at::Tensor bias_ws, part_ws;
+  DlMlmXent a = mlm_xent_desc(t, w, bias, labels, ignore_index, splits, bias_ws, "mlm_xent_eval", 2);
+  if (a.splits > 1) a.part_ws = f32(part_ws = mlm_xent_split_ws(a, 4 * a.splits + 1, t, "mlm_xent_eval"));
   auto row_loss = at::empty({a.M}, t.options().dtype(at::kFloat));
   auto row_rank = at::empty({a.M}, t.options().dtype(at::kInt));
   a.row_loss = f32(row_loss), a.row_rank = row_rank.data_ptr<int>();

@@ -216,7 +216,15 @@ struct DlMlmXent {
   // of columns j with s_j > s_label, or s_j == s_label and j < label, on the fp32 scores (-1 on an
   // ignored row); reads neither lse nor loss
   int* row_rank = nullptr;
+  // vocabulary slices (dl_mlm_xent_splits; 1: the unsplit kernels).  With n > 1 slices and Mp = M
+  // rounded up to 64, scratch: forward part_ws of 3 n Mp floats, evaluation part_ws of (4 n + 1) Mp,
+  // backward dt_ws of n Mp E floats
+  int splits = 1;
+  float* part_ws = nullptr; float* dt_ws = nullptr;
 };
+// slices for a requested `splits` (0: chosen from the row blocks and the device's compute units; n > 0:
+// n, clamped to the 64-row tiles of V); -1 for a negative request
+int dl_mlm_xent_splits(int M, int V, int splits, int compute_units);
 int dl_mlm_xent_fwd(const DlMlmXent& a, hipStream_t st);
 int dl_mlm_xent_eval(const DlMlmXent& a, hipStream_t st);
 int dl_mlm_xent_bwd(const DlMlmXent& a, hipStream_t st);

@@ -30,6 +30,10 @@
 // its bias.  Token rows past M - 1 are loaded as row M - 1, stored nowhere and counted nowhere
 // (scale 0, lse +1e30 in the backward's per-row table).
 // The mean is taken by one block in a fixed order: no float atomics anywhere in this file.
+//
+// fwd, eval and bwd dt also exist in a form that splits the vocabulary across workgroups, for calls
+// whose row blocks alone leave compute units idle ("vocabulary split" below; dl_mlm_xent_splits
+// chooses).  One slice runs exactly the kernels described above.
 #include "dl_attn_tile.h"
 #include "dl_common.h"
 #include "dl_kernels.h"
@@ -511,6 +515,305 @@ __global__ __launch_bounds__(256, 2) void mlm_xent_bwd_dt_kernel(const bf16_t* _
   }
 }
 
+// ------------------------------------------------------------------------------- vocabulary split
+// The kernels above give a workgroup a block of token rows and the whole vocabulary, so a call with
+// few rows runs on a handful of compute units for as long as one workgroup needs for all of V.  The
+// split forms below partition the vocabulary instead (the flash-decoding split): the grid is
+// (128-row blocks, slices), slice s of n owns the whole 64-row tiles [s nt / n, (s + 1) nt / n) of
+// the nt = ceil(V / 64), and every workgroup is the one-sub-block-per-wave form (token on the lane,
+// t fragments in registers, the same two-slot ring) swept over its slice alone.  What a row needs
+// from all of V goes through a workspace and a small streaming kernel, slice by slice in a fixed
+// order: no atomics, and a call repeated gives the same bits.
+//
+//   part    a slice's running max m and sum l (log2 units) and the label's RAW accumulator, 0 in
+//           every slice but the one that holds the label, so the sum over slices is exact.
+//           Workspace part[3][n][Mp]: the merge's lanes read consecutive rows of one slice.
+//   merge   mx = max_s m_s, lse = mx + log2(sum_s l_s 2^(m_s - mx)); the label's log2 score is the
+//           forward's fmaf(acc, log2 e, bias) and the row loss follows as in the forward.  For the
+//           evaluation it also writes the label's natural score sy = acc + bias.
+//   rank    the evaluation's second sweep over a slice, against sy: the tile-below / tile-above /
+//           own-tile thresholds of mlm_xent_eval_kernel work on the global tile index, so they hold
+//           across slices as they are.  Integer counts cnt[n][Mp], summed by mlm_xent_count_kernel.
+//   dt      mlm_xent_bwd_dt_kernel over a slice; the fp32 partial goes to slab[n][Mp][128] and
+//           mlm_xent_dt_reduce_kernel adds the slabs in slice order and rounds to bf16 once.
+constexpr int SPLIT_ROWS = 128;  // rows a workgroup of the split forms owns
+
+__device__ __forceinline__ int slice_tile(int s, int n, int nt) { return (int)((long)s * nt / n); }
+
+__global__ __launch_bounds__(256, 2) void mlm_xent_part_kernel(const bf16_t* __restrict__ t, long ldt,
+                                                                const bf16_t* __restrict__ w, long ldw,
+                                                                const float* __restrict__ biasl2,
+                                                                const long* __restrict__ labels, float* __restrict__ part,
+                                                                int Mp, int M, int V, int ignore_index) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * W_STAGE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int nt = (V + 63) / 64, ns = gridDim.y, sl = blockIdx.y;
+  const int vt0 = slice_tile(sl, ns, nt), vt1 = slice_tile(sl + 1, ns, nt);
+  auto issue = [&](int vt) {  // vocabulary tile vt -> slot vt % NBUF
+    uint8_t* slot = smem + (vt % NBUF) * W_STAGE;
+    dma_block(w, ldw, vt * 64, V, slot, wv, lane);
+    dma_f32x64(biasl2 + vt * 64, slot + 2 * TILE_BYTES, lane);
+  };
+  issue(vt0);
+
+  const int row = blockIdx.x * SPLIT_ROWS + wv * 32 + r;
+  const int rc = min(row, M - 1);
+  bf16x8 tf[1][8];
+  load_row_frags(t, ldt, rc, hh, tf[0]);
+  const long lb = labels[rc];
+  int lab = (row < M && lb != ignore_index && lb >= 0 && lb < V) ? (int)lb : -1;
+  settle(lab);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) settle(tf[0][ks]);
+  float m = NEG_BIG, l = 0.f, xa = 0.f;
+
+  wait_vm_all();
+  for (int vt = vt0; vt < vt1; ++vt) {
+    ring_wait();
+    __syncthreads();
+    if (vt + 1 < vt1) issue(vt + 1);
+    const uint8_t* Ws = smem + (vt % NBUF) * W_STAGE;
+    const float* bs = reinterpret_cast<const float*>(Ws + 2 * TILE_BYTES);
+    floatx16 s[1][2];
+    tile_scores<1>(Ws, tf, r, hh, s);
+    const int d = lab - vt * 64;  // the label's row in this tile
+    if (__ballot((unsigned)d < 64u) != 0) {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (32 * j + crow(i, hh) == d) xa = s[0][j][i];
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) s[0][j][i] = fmaf(s[0][j][i], LOG2E, bs[32 * j + crow(i, hh)]);
+    const float mx = half_max(vmax3(max16(s[0][0]), max16(s[0][1]), m));
+    const float nm = -mx;
+    float rsa[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) rsa[i & 3] += __builtin_amdgcn_exp2f(s[0][j][i] + nm);
+    l = fmaf(l, __builtin_amdgcn_exp2f(m + nm), half_sum((rsa[0] + rsa[1]) + (rsa[2] + rsa[3])));
+    m = mx;
+  }
+  const float acc = half_sum(xa);  // one half found it (in one slice), the other holds 0
+  if (row < M && hh == 0) {
+    float* p = part + (long)sl * Mp + row;
+    p[0] = m;
+    p[(long)ns * Mp] = l;
+    p[2L * ns * Mp] = acc;
+  }
+}
+
+// bias2 = [log2-unit bias | natural bias (sy != nullptr only)], Vp floats each.  lse and sy may be
+// nullptr.  As in the evaluation kernel, a label outside [0, V) that is not ignore_index is never
+// used as an index: its row's loss is NaN.
+__global__ __launch_bounds__(256) void mlm_xent_merge_kernel(const float* __restrict__ part, int ns, int Mp,
+                                                              const float* __restrict__ bias2, int Vp,
+                                                              const long* __restrict__ labels, float* __restrict__ lse,
+                                                              float* __restrict__ row_loss, float* __restrict__ sy, int M,
+                                                              int V, int ignore_index) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= M) return;
+  const float* pm = part + row;
+  const float* pl = pm + (long)ns * Mp;
+  const float* pa = pl + (long)ns * Mp;
+  float mx = NEG_BIG;
+  for (int s = 0; s < ns; ++s) mx = fmaxf(mx, pm[(long)s * Mp]);
+  float l = 0.f, acc = 0.f;
+  for (int s = 0; s < ns; ++s) {
+    l = fmaf(pl[(long)s * Mp], __builtin_amdgcn_exp2f(pm[(long)s * Mp] - mx), l);
+    acc += pa[(long)s * Mp];
+  }
+  const float l2 = mx + log2f(l);
+  const long lb = labels[row];
+  const bool in = lb >= 0 && lb < V;
+  const long li = in ? lb : 0;
+  if (lse) lse[row] = l2;
+  row_loss[row] = lb == ignore_index ? 0.f : (in ? (l2 - fmaf(acc, LOG2E, bias2[li])) * LN2 : __builtin_nanf(""));
+  if (sy) sy[row] = acc + bias2[Vp + li];
+}
+
+__global__ __launch_bounds__(256, 2) void mlm_xent_rank_kernel(const bf16_t* __restrict__ t, long ldt,
+                                                                const bf16_t* __restrict__ w, long ldw,
+                                                                const float* __restrict__ biasn,
+                                                                const long* __restrict__ labels,
+                                                                const float* __restrict__ sy_ws, int* __restrict__ cnt_ws,
+                                                                int Mp, int M, int V, int ignore_index) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * W_STAGE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int nt = (V + 63) / 64, ns = gridDim.y, sl = blockIdx.y;
+  const int vt0 = slice_tile(sl, ns, nt), vt1 = slice_tile(sl + 1, ns, nt);
+  auto issue = [&](int vt) {
+    uint8_t* slot = smem + (vt % NBUF) * W_STAGE;
+    dma_block(w, ldw, vt * 64, V, slot, wv, lane);
+    dma_f32x64(biasn + vt * 64, slot + 2 * TILE_BYTES, lane);
+  };
+  issue(vt0);
+
+  const int row = blockIdx.x * SPLIT_ROWS + wv * 32 + r;
+  const int rc = min(row, M - 1);
+  bf16x8 tf[1][8];
+  load_row_frags(t, ldt, rc, hh, tf[0]);
+  const long lb = labels[rc];
+  int lab = (row < M && lb != ignore_index && lb >= 0 && lb < V) ? (int)lb : -1;
+  float sy = sy_ws[rc];
+  float lo = next_below(sy);
+  settle(lab);
+  settle(sy);
+  settle(lo);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) settle(tf[0][ks]);
+  int cnt = 0;
+
+  wait_vm_all();
+  for (int vt = vt0; vt < vt1; ++vt) {
+    ring_wait();
+    __syncthreads();
+    if (vt + 1 < vt1) issue(vt + 1);
+    const uint8_t* Ws = smem + (vt % NBUF) * W_STAGE;
+    const float* bs = reinterpret_cast<const float*>(Ws + 2 * TILE_BYTES);
+    floatx16 s[1][2];
+    tile_scores<1>(Ws, tf, r, hh, s);
+    const int d = lab - vt * 64;
+    int c4[4] = {0, 0, 0, 0};
+    if (__ballot((unsigned)d < 64u) == 0) {  // no label of this wave's rows in the tile
+      const float thr = d >= 64 ? lo : sy;
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) c4[i & 3] += s[0][j][i] + bs[32 * j + crow(i, hh)] > thr ? 1 : 0;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const int col = 32 * j + crow(i, hh);
+          c4[i & 3] += s[0][j][i] + bs[col] > (col < d ? lo : sy) ? 1 : 0;
+        }
+    }
+    cnt += (c4[0] + c4[1]) + (c4[2] + c4[3]);
+  }
+  const int total = half_sum_int(cnt);
+  if (row < M && hh == 0) cnt_ws[(long)sl * Mp + row] = total;
+}
+
+__global__ __launch_bounds__(256) void mlm_xent_count_kernel(const int* __restrict__ cnt_ws, int ns, int Mp,
+                                                              const long* __restrict__ labels,
+                                                              int* __restrict__ row_rank, int M, int V,
+                                                              int ignore_index) {
+  const int row = blockIdx.x * blockDim.x + threadIdx.x;
+  if (row >= M) return;
+  int c = 0;
+  for (int s = 0; s < ns; ++s) c += cnt_ws[(long)s * Mp + row];
+  const long lb = labels[row];
+  row_rank[row] = (lb != ignore_index && lb >= 0 && lb < V) ? c : -1;
+}
+
+__global__ __launch_bounds__(256, 2) void mlm_xent_bwd_dt_part_kernel(const bf16_t* __restrict__ t, long ldt,
+                                                                       const bf16_t* __restrict__ w, long ldw,
+                                                                       const float* __restrict__ biasl2,
+                                                                       const float* __restrict__ info, int Mp,
+                                                                       float* __restrict__ slab, int M, int V) {
+  __shared__ __attribute__((aligned(16))) uint8_t smem[NBUF * W_STAGE];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
+  const int nt = (V + 63) / 64, ns = gridDim.y, sl = blockIdx.y;
+  const int vt0 = slice_tile(sl, ns, nt), vt1 = slice_tile(sl + 1, ns, nt);
+  auto issue = [&](int vt) {
+    uint8_t* slot = smem + (vt % NBUF) * W_STAGE;
+    dma_block(w, ldw, vt * 64, V, slot, wv, lane);
+    dma_f32x64(biasl2 + vt * 64, slot + 2 * TILE_BYTES, lane);
+  };
+  issue(vt0);
+
+  const int row = blockIdx.x * SPLIT_ROWS + wv * 32 + r;
+  const int rc = min(row, M - 1);
+  bf16x8 tf[8];
+  load_row_frags(t, ldt, rc, hh, tf);
+  float l2 = info[rc];
+  float gs = row < M ? info[Mp + rc] : 0.f;
+  int lab = row < M ? reinterpret_cast<const int*>(info)[2 * (long)Mp + rc] : -1;
+  settle(l2);
+  settle(gs);
+  settle(lab);
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) settle(tf[ks]);
+  floatx16 o[4];
+#pragma unroll
+  for (int c = 0; c < 4; ++c) zero(o[c]);
+
+  wait_vm_all();
+  for (int vt = vt0; vt < vt1; ++vt) {
+    ring_wait();
+    __syncthreads();
+    if (vt + 1 < vt1) issue(vt + 1);
+    const uint8_t* Ws = smem + (vt % NBUF) * W_STAGE;
+    const float* bs = reinterpret_cast<const float*>(Ws + 2 * TILE_BYTES);
+    floatx16 s[2];
+    zero(s[0]);
+    zero(s[1]);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int ks = 0; ks < 8; ++ks) s[j] = mfma32(block_row_frag(Ws, 32 * j + r, ks, hh), tf[ks], s[j]);
+    const int d = lab - vt * 64;
+    if (__ballot((unsigned)d < 64u) == 0) {  // no label of this wave's rows in the tile: dS = P g / count
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          s[j][i] = __builtin_amdgcn_exp2f(fmaf(s[j][i], LOG2E, bs[32 * j + crow(i, hh)] - l2)) * gs;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+          const float p = __builtin_amdgcn_exp2f(fmaf(s[j][i], LOG2E, bs[32 * j + crow(i, hh)] - l2));
+          s[j][i] = (p - (32 * j + crow(i, hh) == d ? 1.f : 0.f)) * gs;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int ss = 0; ss < 2; ++ss) {
+        const bf16x8 pb = pack_acc(s[j], ss);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[c] = mfma32(block_tr(Ws, 32 * j + 16 * ss, hh, c, lane), pb, o[c]);
+      }
+  }
+  if (row < M) {
+    float* op = slab + ((long)sl * Mp + row) * E;
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int v = 0; v < 4; ++v)
+        *reinterpret_cast<float4*>(op + 32 * c + 8 * v + 4 * hh) =
+            make_float4(o[c][4 * v], o[c][4 * v + 1], o[c][4 * v + 2], o[c][4 * v + 3]);
+  }
+}
+
+// dt[row] = bf16(sum over slices, in slice order, of slab[s][row]): a thread takes 8 columns of a
+// row (two 16-byte loads per slice, one 16-byte store), so a wave reads 2 KiB in a row per slice
+__global__ __launch_bounds__(256) void mlm_xent_dt_reduce_kernel(const float* __restrict__ slab, int ns, int Mp,
+                                                                  bf16_t* __restrict__ dt, long lddt, int M) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long row = i >> 4;
+  const int c8 = (int)(i & 15) * 8;
+  if (row >= M) return;
+  const float4* p = reinterpret_cast<const float4*>(slab + row * E + c8);
+  float4 a = p[0], b = p[1];
+  for (int s = 1; s < ns; ++s) {
+    const float4* q = p + (long)s * Mp * (E / 4);
+    const float4 x = q[0], y = q[1];
+    a.x += x.x, a.y += x.y, a.z += x.z, a.w += x.w;
+    b.x += y.x, b.y += y.y, b.z += y.z, b.w += y.w;
+  }
+  const uint2 lo = pack4(a.x, a.y, a.z, a.w), hi = pack4(b.x, b.y, b.z, b.w);
+  *reinterpret_cast<uint4*>(dt + row * lddt + c8) = make_uint4(lo.x, lo.y, hi.x, hi.y);
+}
+
 // ------------------------------------------------------------------------------------------ bwd dw
 __global__ __launch_bounds__(256, 2) void mlm_xent_bwd_dw_kernel(const bf16_t* __restrict__ t, long ldt,
                                                                   const bf16_t* __restrict__ w, long ldw,
@@ -622,22 +925,78 @@ static void mlm_bias(const DlMlmXent& a, hipStream_t st) {
   mlm_bias_kernel<><<<(Vp + 255) / 256, 256, 0, st>>>(a.bias, a.bias_bf16, a.bias_ws, a.V, Vp);
 }
 
+// The number of vocabulary slices a call runs with: `splits` > 0 forces it (clamped to the tiles of
+// V and the grid's y limit), 0 chooses, from the sweeps of forced counts in
+// profiles/mlm_head_split.jsonl (V = 30000, M = 308 .. 157696, 256 compute units):
+//   - the split forms make ceil(M / 128) row blocks, and slices are added while the grid still fits
+//     SPLIT_FILL workgroups per compute unit, one resident wave of workgroups: at 39 row blocks 13
+//     slices (507 workgroups) take 291 us forward + backward, 16 slices 319 us, 8 slices 351 us;
+//   - a slice keeps at least SPLIT_MIN_TILES tiles, a workgroup's fixed cost (its t fragments, the
+//     ring's first stage, its workspace rows): at 10 row blocks 29 slices take 167 us, 58 take 189 us.
+//     A vocabulary of fewer than 128 SPLIT_MIN_TILES rows is therefore never split;
+//   - with more row blocks than that fill leaves SPLIT_MANY slices for, SPLIT_MANY slices still even
+//     out the last wave of workgroups (M = 39424: 1.91 ms against 2.50 ms unsplit; 8 slices 1.86 ms).
+//     That held up to the largest M measured, 157696 (7.7 ms against 8.1 ms); past
+//     SPLIT_MANY_BLOCKS row blocks per compute unit nothing was measured, the dt slabs pass half a
+//     gigabyte, and the call stays unsplit.
+// -1: a negative `splits`.
+constexpr int SPLIT_FILL = 2, SPLIT_MIN_TILES = 16, SPLIT_MANY = 4, SPLIT_MANY_BLOCKS = 8;
+int dl_mlm_xent_splits(int M, int V, int splits, int compute_units) {
+  const int nt = (V + 63) / 64;
+  if (splits < 0) return -1;
+  if (splits > 0) return std::min(splits, std::min(nt, 65535));
+  const int rb = std::max((M + SPLIT_ROWS - 1) / SPLIT_ROWS, 1);
+  int n = SPLIT_FILL * compute_units / rb;
+  if (n < SPLIT_MANY) n = rb <= SPLIT_MANY_BLOCKS * compute_units ? SPLIT_MANY : 1;
+  return std::max(1, std::min(n, nt / SPLIT_MIN_TILES));
+}
+
+// slices of this call (1: the unsplit kernels), 0 when the workspace a split needs is missing
+static int mlm_slices(const DlMlmXent& a, const void* ws) {
+  const int n = a.M > 0 ? dl_mlm_xent_splits(a.M, a.V, std::max(a.splits, 1), 0) : 1;
+  return n > 1 && ws == nullptr ? 0 : n;
+}
+
 int dl_mlm_xent_fwd(const DlMlmXent& a, hipStream_t st) {
-  if (!mlm_xent_ok(a)) return -1;
+  const int n = mlm_slices(a, a.part_ws);
+  if (!mlm_xent_ok(a) || n == 0) return -1;
   if (a.M > 0) {
     mlm_bias(a, st);
-    mlm_xent_fwd_kernel<<<(a.M + FWD_ROWS - 1) / FWD_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.labels,
-                                                                         a.lse, a.row_loss, a.M, a.V, a.ignore_index);
+    if (n == 1) {
+      mlm_xent_fwd_kernel<<<(a.M + FWD_ROWS - 1) / FWD_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.labels,
+                                                                           a.lse, a.row_loss, a.M, a.V, a.ignore_index);
+    } else {
+      const int Mp = (a.M + 63) / 64 * 64;
+      mlm_xent_part_kernel<<<dim3((a.M + SPLIT_ROWS - 1) / SPLIT_ROWS, n), 256, 0, st>>>(
+          a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.labels, a.part_ws, Mp, a.M, a.V, a.ignore_index);
+      mlm_xent_merge_kernel<<<(a.M + 255) / 256, 256, 0, st>>>(a.part_ws, n, Mp, a.bias_ws, 0, a.labels, a.lse,
+                                                               a.row_loss, nullptr, a.M, a.V, a.ignore_index);
+    }
   }
   mlm_loss_kernel<<<1, 1024, 0, st>>>(a.row_loss, a.labels, a.M, a.ignore_index, a.loss);
   return 0;
 }
 
 int dl_mlm_xent_eval(const DlMlmXent& a, hipStream_t st) {
-  if (!mlm_xent_ok(a)) return -1;
+  const int n = mlm_slices(a, a.part_ws);
+  if (!mlm_xent_ok(a) || n == 0) return -1;
   if (a.M == 0) return 0;
   const int Vp = (a.V + 63) / 64 * 64;
   mlm_bias_kernel<true><<<(Vp + 255) / 256, 256, 0, st>>>(a.bias, a.bias_bf16, a.bias_ws, a.V, Vp);
+  if (n > 1) {  // two launches: the rank sweep needs the label's score, which another slice may hold
+    const int Mp = (a.M + 63) / 64 * 64;
+    const dim3 grid((a.M + SPLIT_ROWS - 1) / SPLIT_ROWS, n);
+    float* sy = a.part_ws + 3L * n * Mp;
+    int* cnt = reinterpret_cast<int*>(sy + Mp);
+    mlm_xent_part_kernel<<<grid, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.labels, a.part_ws, Mp, a.M, a.V,
+                                               a.ignore_index);
+    mlm_xent_merge_kernel<<<(a.M + 255) / 256, 256, 0, st>>>(a.part_ws, n, Mp, a.bias_ws, Vp, a.labels, nullptr,
+                                                             a.row_loss, sy, a.M, a.V, a.ignore_index);
+    mlm_xent_rank_kernel<<<grid, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws + Vp, a.labels, sy, cnt, Mp, a.M, a.V,
+                                               a.ignore_index);
+    mlm_xent_count_kernel<<<(a.M + 255) / 256, 256, 0, st>>>(cnt, n, Mp, a.labels, a.row_rank, a.M, a.V, a.ignore_index);
+    return 0;
+  }
   // A workgroup walks the whole vocabulary twice, so the call takes as long as one workgroup does:
   // while 256-row blocks would leave compute units idle, 128-row blocks (one sub-block per wave)
   // halve the work per tile and double the workgroups
@@ -651,13 +1010,20 @@ int dl_mlm_xent_eval(const DlMlmXent& a, hipStream_t st) {
 }
 
 int dl_mlm_xent_bwd(const DlMlmXent& a, hipStream_t st) {
-  if (!mlm_xent_ok(a) || (a.gw == nullptr) != (a.gb == nullptr)) return -1;
+  const int n = mlm_slices(a, a.dt_ws);
+  if (!mlm_xent_ok(a) || n == 0 || (a.gw == nullptr) != (a.gb == nullptr)) return -1;
   if (a.M == 0) return 0;
   const int Mp = (a.M + 63) / 64 * 64;
   mlm_bias(a, st);
   mlm_rows_kernel<<<1, 1024, 0, st>>>(a.lse, a.labels, a.gloss, a.M, Mp, a.ignore_index, a.row_ws);
-  mlm_xent_bwd_dt_kernel<<<(a.M + DT_ROWS - 1) / DT_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.row_ws, Mp,
-                                                                        a.dt, a.lddt, a.M, a.V);
+  if (n == 1) {
+    mlm_xent_bwd_dt_kernel<<<(a.M + DT_ROWS - 1) / DT_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.row_ws,
+                                                                          Mp, a.dt, a.lddt, a.M, a.V);
+  } else {
+    mlm_xent_bwd_dt_part_kernel<<<dim3((a.M + SPLIT_ROWS - 1) / SPLIT_ROWS, n), 256, 0, st>>>(
+        a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.row_ws, Mp, a.dt_ws, a.M, a.V);
+    mlm_xent_dt_reduce_kernel<<<(a.M + 15) / 16, 256, 0, st>>>(a.dt_ws, n, Mp, a.dt, a.lddt, a.M);
+  }
   if (a.gw)
     mlm_xent_bwd_dw_kernel<<<(a.V + DW_ROWS - 1) / DW_ROWS, 256, 0, st>>>(a.t, a.ldt, a.w, a.ldw, a.bias_ws, a.row_ws,
                                                                           Mp, a.gw, a.gb, a.M, a.V);

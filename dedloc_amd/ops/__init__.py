@@ -331,31 +331,36 @@ def cross_entropy(logits, labels, ignore_index=-100):
 
 class _MlmCrossEntropy(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, t, w, bias, labels, gw, gb, ignore_index):
-        loss, lse = OPS.mlm_xent_fwd(t, w, bias, labels, ignore_index)
+    def forward(ctx, t, w, bias, labels, gw, gb, ignore_index, splits):
+        loss, lse = OPS.mlm_xent_fwd(t, w, bias, labels, ignore_index, splits)
         ctx.save_for_backward(t, w, bias, labels, lse)
-        ctx.gw, ctx.gb, ctx.ignore_index = gw, gb, ignore_index
+        ctx.gw, ctx.gb, ctx.ignore_index, ctx.splits = gw, gb, ignore_index, splits
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
         t, w, bias, labels, lse = ctx.saved_tensors
-        dt = OPS.mlm_xent_bwd(t, w, bias, labels, lse, dloss.reshape(1).float(), ctx.gw, ctx.gb, ctx.ignore_index)
-        return dt, None, None, None, None, None, None
+        dt = OPS.mlm_xent_bwd(t, w, bias, labels, lse, dloss.reshape(1).float(), ctx.gw, ctx.gb, ctx.ignore_index,
+                              ctx.splits)
+        return dt, None, None, None, None, None, None, None
 
 
-def mlm_cross_entropy(t, w, bias, labels, gw=None, gb=None, ignore_index=-100):
+def mlm_cross_entropy(t, w, bias, labels, gw=None, gb=None, ignore_index=-100, splits=0):
     """``cross_entropy(linear(t, w, bias), labels)`` for the tied MLM decoder without the [M, V]
     logits: t [M, 128] bf16, w [V, 128] bf16, bias [V].  The logits stay fp32 inside the kernels
     (the composed path rounds them to bf16); the backward recomputes them from t, the saved
     log-sum-exp and the labels, returns dt and adds the weight and bias gradients into the fp32
-    views ``gw`` [V, 128] / ``gb`` [V] (both or neither; without them only dt is computed)."""
+    views ``gw`` [V, 128] / ``gb`` [V] (both or neither; without them only dt is computed).
+    ``splits`` is the number of vocabulary slices the forward and dt kernels spread over workgroups:
+    0 lets the launcher choose from M and the device's compute units, 1 is the unsplit kernels."""
     if t.dim() != 2 or t.shape[1] != 128 or w.shape[1] != 128:
         raise ValueError(f"mlm_cross_entropy needs an embedding size of 128, got t {tuple(t.shape)}, w {tuple(w.shape)}")
     if (gw is None) != (gb is None):
         raise ValueError("mlm_cross_entropy: gw and gb come together")
+    if splits < 0:
+        raise ValueError(f"mlm_cross_entropy: splits = {splits} must be 0 (automatic) or positive")
     return _MlmCrossEntropy.apply(t.contiguous(), w, bias.contiguous(), labels.reshape(-1).contiguous(), gw, gb,
-                                  ignore_index)
+                                  ignore_index, int(splits))
 
 
 @torch.no_grad()
@@ -379,18 +384,22 @@ def _eval_sums(row_loss, row_rank, topk):
 
 
 @torch.no_grad()
-def mlm_eval_cross_entropy(t, w, bias, labels, ignore_index=-100, topk=(1, 5)):
+def mlm_eval_cross_entropy(t, w, bias, labels, ignore_index=-100, topk=(1, 5), splits=0):
     """``eval_cross_entropy(linear(t, w, bias), labels)`` for the tied MLM decoder without the [M, V]
     logits (the ``mlm_xent_eval`` kernel: two sweeps over the vocabulary in one launch, the loss from
-    the first and the label's rank from the second).  t [M, 128] bf16 with unit column stride (a
+    the first and the label's rank from the second; with ``splits`` vocabulary slices, 0 = chosen by
+    the launcher, one launch per sweep with the slices spread over workgroups).  t [M, 128] bf16 with unit column stride (a
     strided row view is read in place), w [V, 128] bf16, bias [V].  The scores stay fp32, so the
     ranks are those of the unrounded logits.  Returns what ``eval_cross_entropy`` returns."""
     if t.dim() != 2 or w.dim() != 2 or t.shape[1] != 128 or w.shape[1] != 128:
         raise ValueError(f"mlm_eval_cross_entropy needs an embedding size of 128, got t {tuple(t.shape)}, "
                          f"w {tuple(w.shape)}")
+    if splits < 0:
+        raise ValueError(f"mlm_eval_cross_entropy: splits = {splits} must be 0 (automatic) or positive")
     if t.stride(1) != 1:
         t = t.contiguous()
-    return _eval_sums(*OPS.mlm_xent_eval(t, w, bias.contiguous(), labels.reshape(-1).contiguous(), ignore_index), topk)
+    return _eval_sums(*OPS.mlm_xent_eval(t, w, bias.contiguous(), labels.reshape(-1).contiguous(), ignore_index,
+                                         int(splits)), topk)
 
 
 @torch.no_grad()

@@ -43,10 +43,10 @@ _SCHEMAS = [
     "embed_bwd(Tensor ds, Tensor ids, Tensor? tt, Tensor(a!) dwemb, Tensor(b!) dpemb, Tensor(c!) dtemb, int S) -> ()",
     "xent_fwd_bwd(Tensor logits, Tensor labels, bool inplace, int ignore_index) -> (Tensor, Tensor)",
     "xent_eval(Tensor logits, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
-    "mlm_xent_fwd(Tensor t, Tensor w, Tensor bias, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
+    "mlm_xent_fwd(Tensor t, Tensor w, Tensor bias, Tensor labels, int ignore_index, int splits=0) -> (Tensor, Tensor)",
     "mlm_xent_bwd(Tensor t, Tensor w, Tensor bias, Tensor labels, Tensor lse, Tensor gloss, Tensor(a!)? gw, "
-    "Tensor(b!)? gb, int ignore_index) -> Tensor",
-    "mlm_xent_eval(Tensor t, Tensor w, Tensor bias, Tensor labels, int ignore_index) -> (Tensor, Tensor)",
+    "Tensor(b!)? gb, int ignore_index, int splits=0) -> Tensor",
+    "mlm_xent_eval(Tensor t, Tensor w, Tensor bias, Tensor labels, int ignore_index, int splits=0) -> (Tensor, Tensor)",
     "knn_topk(Tensor q, Tensor bank, int k, int splits=0) -> (Tensor, Tensor)",
     "knn_vote(Tensor vals, Tensor idx, Tensor bank_labels, Tensor targets, int num_classes, float sigma) "
     "-> (Tensor, Tensor)",
@@ -550,8 +550,9 @@ def _xent_eval_cpu(logits, labels, ignore_index):
 
 
 @_impl("mlm_xent_fwd")
-def _mlm_xent_fwd_cpu(t, w, bias, labels, ignore_index):
-    """logits = t w^T + bias in fp32 (never rounded to bf16): the mean loss over the live rows (0
+def _mlm_xent_fwd_cpu(t, w, bias, labels, ignore_index, splits=0):
+    """``splits`` (here and below) is the GPU kernels' schedule and does not change the result.
+    logits = t w^T + bias in fp32 (never rounded to bf16): the mean loss over the live rows (0
     without one) and lse [M] in log2 units, as the kernel stores it."""
     x = t.float() @ w.float().t() + bias.float()
     lab = labels.reshape(-1)
@@ -564,7 +565,7 @@ def _mlm_xent_fwd_cpu(t, w, bias, labels, ignore_index):
 
 
 @_impl("mlm_xent_bwd")
-def _mlm_xent_bwd_cpu(t, w, bias, labels, lse, gloss, gw, gb, ignore_index):
+def _mlm_xent_bwd_cpu(t, w, bias, labels, lse, gloss, gw, gb, ignore_index, splits=0):
     """dS = (softmax - onehot) gloss / live rows, rounded to bf16 as the kernels pack it: returns
     dt = dS w (bf16) and adds dS^T t into gw, the column sums of dS into gb."""
     x = t.float() @ w.float().t() + bias.float()
@@ -584,7 +585,7 @@ def _mlm_xent_bwd_cpu(t, w, bias, labels, lse, gloss, gw, gb, ignore_index):
 
 
 @_impl("mlm_xent_eval")
-def _mlm_xent_eval_cpu(t, w, bias, labels, ignore_index):
+def _mlm_xent_eval_cpu(t, w, bias, labels, ignore_index, splits=0):
     """``xent_eval`` on logits = t w^T + bias kept in fp32 (never rounded to bf16): per row the loss
     and the number of columns that beat the label, ties to the lower index; ignored rows are (0, -1)."""
     if t.dim() != 2 or w.dim() != 2 or t.shape[1] != w.shape[1] or labels.numel() != t.shape[0]:
