@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--length_mode", default="full", choices=["full", "wikitext", "uniform"])
     ap.add_argument("--min_len", type=int, default=64, help="shortest row of --length_mode wikitext / uniform")
     ap.add_argument("--pack_sequences", action="store_true", help="packed, padding-free batches (dedloc only)")
+    ap.add_argument("--packed_last_layer_rows", action="store_true",
+                    help="with --pack_sequences: the last layer on the rows the heads read (forward's last_layer_rows)")
     ap.add_argument("--batches", type=int, default=4, help="distinct batches cycled when lengths vary")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--attn", default="fused", choices=["fused", "composed"],
@@ -97,6 +99,8 @@ def main():
             ids, tt, am, pos, lab, sop, lens = data[calls[0] % len(data)]
             calls[0] += 1
             extra = {"pack_sequences": True, "lengths": lens} if args.pack_sequences else {}
+            if args.packed_last_layer_rows:
+                extra["last_layer_rows"] = True
             out = model(ids, am, tt, sentence_order_label=sop, mlm_positions=pos, mlm_labels=lab, **extra)
             out["loss"].backward()
             return out["loss"]
@@ -151,7 +155,8 @@ def main():
     fl = flops_per_sample(cfg, args.seq, P) * args.batch  # counted on full rows, whatever the lengths
     print(json.dumps({"impl": args.impl, "config": args.config, "attn": args.attn, "mlm_loss": args.mlm_loss, "batch": args.batch, "seq": args.seq, "ms_per_microstep": dt * 1e3,
                       "samples_per_s": args.batch / dt, "tflops": fl / dt / 1e12, "loss": float(loss.detach()),
-                      "length_mode": args.length_mode, "pack_sequences": bool(args.pack_sequences), **shares}), flush=True)
+                      "length_mode": args.length_mode, "pack_sequences": bool(args.pack_sequences),
+                      "packed_last_layer_rows": bool(args.packed_last_layer_rows), **shares}), flush=True)
 
 
 if __name__ == "__main__":

@@ -131,7 +131,8 @@ FILE_FLAGS: dict = {"comm_q8.hip": ["-ffp-contract=on"],
                     "mlm_xent.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
                     "pool_eval.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]}
 # kernel files that include another kernel file (for its templates): rebuilt when that one changes
-HIP_INCLUDES: dict = {"attention_compact_q.hip": ["attention.hip"]}
+HIP_INCLUDES: dict = {"attention_compact_q.hip": ["attention.hip"],
+                      "attention_varlen_compact_q.hip": ["attention.hip"]}
 
 
 def _link(objs, out, tlib, verbose):

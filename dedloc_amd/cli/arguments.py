@@ -110,6 +110,7 @@ class AlbertTrainingArguments:
     eval_steps: int = field(default=0, metadata={"help": "with --do_eval: evaluate every this many collaborative steps (0 = only at the end of training)"})
     eval_max_batches: int = field(default=8, metadata={"help": "with --do_eval: batches of per_device_eval_batch_size per evaluation"})
     pack_sequences: bool = field(default=False, metadata={"help": "run the model on packed, padding-free batches (variable shapes per batch; one device sync per batch when the data stream has no host-side lengths)"})
+    packed_last_layer_rows: bool = field(default=False, metadata={"help": "with --pack_sequences (head_dim 64): run the last ALBERT layer only on the rows the MLM and SOP heads read"})
     # ---- MI355X emulation of the reference's heterogeneous AWS fleet
     throttle: float = field(default=0.0, metadata={"help": "extra idle seconds per training step (emulates a slower peer)"})
     slowdown: float = field(default=1.0, metadata={"help": "emulate slower hardware: each step takes this many times longer"})

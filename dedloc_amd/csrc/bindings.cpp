@@ -574,7 +574,8 @@ std::tuple<at::Tensor, at::Tensor> knn_vote(const at::Tensor& vals, const at::Te
 
 // ------------------------------------------------------------------ attention
 // Every fused call is one DlAttn descriptor (dl_kernels.h) handed to attn_route below, the only
-// place that calls the launchers of attention.hip, attention_compact_q.hip and attention_hd128.hip.
+// place that calls the launchers of attention.hip, attention_compact_q.hip,
+// attention_varlen_compact_q.hip and attention_hd128.hip.
 inline const int* kvinfo_ptr(const c10::optional<at::Tensor>& kvinfo, int64_t B) {
   if (!kvinfo.has_value()) return nullptr;
   expect(*kvinfo, at::kInt, "kvinfo");
@@ -599,12 +600,14 @@ inline void fixed_mask(DlAttn& a, const c10::optional<at::Tensor>& mbias, const 
 }
 
 // The one place an attention kernel is chosen: head_dim 128 runs in attention_hd128.hip, head_dim
-// 64 in attention.hip or, with compact queries, in attention_compact_q.hip.  There are no other
+// 64 in attention.hip or, with compact queries, in attention_compact_q.hip (fixed-S keys) and
+// attention_varlen_compact_q.hip (packed keys).  There are no other
 // fused kernels (ops.FUSED_HEAD_DIMS): every other head size goes through ops.attn_composed_*.
 void attn_route(const DlAttn& a, bool bwd, const char* what, hipStream_t st) {
   if (a.q) {
-    TORCH_CHECK(a.D == 64 && !a.seqinfo, "dedloc_amd: ", what,
-                ": compact queries exist for head_dim 64 only, on the fixed-S layout");
+    TORCH_CHECK(a.D == 64, "dedloc_amd: ", what, ": compact queries exist for head_dim 64 only (got head_dim ", a.D,
+                ")");
+    if (a.seqinfo) return check(bwd ? dl_attn_hd64qv_bwd(a, st) : dl_attn_hd64qv_fwd(a, st), what);
     return check(bwd ? dl_attn_hd64q_bwd(a, st) : dl_attn_hd64q_fwd(a, st), what);
   }
   TORCH_CHECK((a.D == 64 || a.D == 128) && a.ld == 3L * a.H * a.D, "dedloc_amd: ", what, ": head_dim ", a.D,
@@ -778,6 +781,62 @@ at::Tensor attn_varlen_bwd(const at::Tensor& qkv, const at::Tensor& seqinfo, con
   a.dbias = opt_f32(dbias, a.ld, "dbias", "3*H*D values", "attn_varlen_bwd");
   attn_route(a, true, "attn_varlen_bwd", cur_stream(qkv));
   return dqkv;
+}
+
+// Compact queries over a packed batch: kv [T, 2*H*64] (K | V, any 16-byte aligned row stride) in the
+// packed layout of seqinfo; q [n*Sq, H*64] holds sequence b's queries in the first qcnt[b] rows of its
+// slot of Sq rows, for every one of the n sequences of seqinfo (the dummy tails too, with qcnt 0).
+// Sq may exceed a sequence's slot; qcnt[b] <= min(Sq, slot b) is the caller's (device-side) contract.
+inline DlAttn compact_packed_layout(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt,
+                                    const at::Tensor& seqinfo, const at::Tensor& seqinfo_host, int64_t H, int64_t Sq,
+                                    double scale, const char* what) {
+  expect(q, at::kBFloat16, "q");
+  expect(qcnt, at::kInt, "qcnt");
+  TORCH_CHECK(kv.is_cuda() && kv.scalar_type() == at::kBFloat16 && kv.dim() == 2 && kv.stride(1) == 1, what,
+              ": kv must be a 2-D bf16 GPU tensor with unit column stride");
+  TORCH_CHECK(H >= 1 && kv.size(1) % (2 * H) == 0, what, ": kv must have 2*H*D columns");
+  const int64_t T = kv.size(0), D = kv.size(1) / (2 * H), ld = kv.stride(0);
+  DlAttn a;
+  a.kv = reinterpret_cast<const bf16_t*>(kv.data_ptr()), a.ld = ld;
+  a.H = (int)H, a.D = (int)D, a.scale = (float)scale, a.ldo = H * D;
+  a.q = cbf(q), a.qcnt = qcnt.data_ptr<int>(), a.Sq = (int)Sq;
+  packed_layout(a, seqinfo, seqinfo_host, T, what);
+  TORCH_CHECK(ld >= 2 * H * D && ld % 8 == 0 && reinterpret_cast<uintptr_t>(kv.data_ptr()) % 16 == 0, what,
+              ": kv rows must be 16-byte aligned");
+  TORCH_CHECK(Sq >= 64 && Sq % 64 == 0, what, ": the query slot Sq = ", Sq, " must be a positive multiple of 64");
+  TORCH_CHECK(q.dim() == 2 && q.size(1) == H * D && q.size(0) == a.B * Sq, what, ": q must be [n*Sq, H*D] for the ",
+              a.B, " sequences of seqinfo");
+  TORCH_CHECK(qcnt.numel() == a.B, what, ": qcnt must be int32[n] (one count per sequence of seqinfo)");
+  return a;
+}
+
+std::tuple<at::Tensor, at::Tensor> attn_varlen_fwd_q(const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt,
+                                                     const at::Tensor& seqinfo, const at::Tensor& seqinfo_host,
+                                                     int64_t H, int64_t Sq, double scale) {
+  DlAttn a = compact_packed_layout(q, kv, qcnt, seqinfo, seqinfo_host, H, Sq, scale, "attn_varlen_fwd_q");
+  auto out = at::empty_like(q);
+  auto lse = at::empty({a.B, H, Sq}, q.options().dtype(at::kFloat));
+  a.out = bf(out), a.lse = f32(lse);
+  attn_route(a, false, "attn_varlen_fwd_q", cur_stream(q));
+  return {out, lse};
+}
+
+// returns (dq [n*Sq, H*D], dkv [T, 2*H*D], delta [n, H, Sq]); past qcnt[b] dq rows are zero and delta
+// entries are not written; dkv rows past a key length, and every row of a sequence with qcnt 0, are zero
+std::tuple<at::Tensor, at::Tensor, at::Tensor> attn_varlen_bwd_q(
+    const at::Tensor& q, const at::Tensor& kv, const at::Tensor& qcnt, const at::Tensor& seqinfo,
+    const at::Tensor& seqinfo_host, const at::Tensor& out, const at::Tensor& dout, const at::Tensor& lse, int64_t H,
+    int64_t Sq, double scale, const c10::optional<at::Tensor>& dbias) {
+  DlAttn a = compact_packed_layout(q, kv, qcnt, seqinfo, seqinfo_host, H, Sq, scale, "attn_varlen_bwd_q");
+  bwd_inputs(a, out, dout, lse, q.numel(), (int64_t)a.B * H * Sq, "attn_varlen_bwd_q",
+             "[n*Sq, H*D] and lse [n, H, Sq]");
+  auto dq = at::empty_like(q);
+  auto dkv = at::empty({kv.size(0), 2 * a.ldo}, q.options());
+  auto delta = at::empty({a.B, H, Sq}, q.options().dtype(at::kFloat));
+  a.delta = f32(delta), a.dq = bf(dq), a.dkv = bf(dkv);
+  a.dbias = opt_f32(dbias, 3 * a.ldo, "dbias", "3*H*D values", "attn_varlen_bwd_q");
+  attn_route(a, true, "attn_varlen_bwd_q", cur_stream(q));
+  return {dq, dkv, delta};
 }
 
 // composed attention (head sizes other than 64): row softmax over GEMM-produced fp32 scores
@@ -2192,6 +2251,8 @@ TORCH_LIBRARY_IMPL(dedloc, CUDA, m) {
   m.impl("attn_bwd_q", &attn_bwd_q);
   m.impl("attn_varlen_fwd", &attn_varlen_fwd);
   m.impl("attn_varlen_bwd", &attn_varlen_bwd);
+  m.impl("attn_varlen_fwd_q", &attn_varlen_fwd_q);
+  m.impl("attn_varlen_bwd_q", &attn_varlen_bwd_q);
   m.impl("embed_ln_pos_fwd", &embed_ln_pos_fwd);
   m.impl("embed_pos_bwd", &embed_pos_bwd);
   m.impl("attn_softmax_fwd", &attn_softmax_fwd);

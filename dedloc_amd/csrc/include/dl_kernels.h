@@ -154,17 +154,22 @@ int dl_gemm(const DlGemm& g, hipStream_t st);
 
 // One fused flash-attention call, forward or backward (bf16 in / out, fp32 softmax state).  Which
 // form it is follows from the pointers that are set: `seqinfo` selects the packed layout, `q` the
-// compact queries; neither is the fixed-S form over the fused QKV buffer.
+// compact queries (both: compact queries over packed keys and values, head_dim 64); neither is the
+// fixed-S form over the fused QKV buffer.
 struct DlAttn {
   // Keys / values: the fused QKV buffer [rows, ld] (Q | K | V, head h at columns h*D of each third;
   // rows = B*S, packed: T), which then holds the queries too; with compact queries K's first column
-  // in the [B*S, ld] key / value buffer (V starts H*D columns after it).  Rows are 16-byte aligned.
+  // in the [B*S, ld] (packed: [T, ld]) key / value buffer (V starts H*D columns after it).  Rows are
+  // 16-byte aligned.
   const bf16_t* kv = nullptr; long ld = 0;
   // Compact queries (head_dim 64, fixed-S layout): sequence b's queries are the first qcnt[b] rows of
   // its slot of Sq rows (Sq % 64 == 0, 64 <= Sq <= S) in q [B*Sq, ldo]; out / dout / dq share that
   // layout, lse / delta are [B, H, Sq]; dkv is [B*S, 2*H*D] (dK | dV, all keys).  Slot rows past
   // qcnt[b] are dead: clamped on load, absent from lse / delta, dK / dV and the bias gradients, and
   // stored as zeros in out / dq.  dq and dkv are the backward's outputs in place of dqkv.
+  // With seqinfo: B slots of Sq rows, one per sequence of seqinfo (the dummy tails too); Sq may exceed
+  // a sequence's slot (qcnt[b] <= Sq and qcnt[b] <= slot b), qcnt[b] == 0 is legal (zeros in that
+  // slot of out / dq and in that sequence's rows of dkv), and dkv is [T, 2*H*D].
   const bf16_t* q = nullptr; const int* qcnt = nullptr; int Sq = 0;
   bf16_t* dq = nullptr; bf16_t* dkv = nullptr;
   // Fixed-S mask (both optional): mbias fp32 [B, S], the additive key bias; kvinfo int32[B + 1], the
@@ -187,12 +192,15 @@ struct DlAttn {
 };
 
 // attention.hip (head_dim 64: fixed-S and packed), attention_compact_q.hip (head_dim 64 with compact
-// queries), attention_hd128.hip (head_dim 128: fixed-S and packed).  Each checks what its kernels
+// queries), attention_varlen_compact_q.hip (head_dim 64 with compact queries over packed keys and
+// values: hd64qv), attention_hd128.hip (head_dim 128: fixed-S and packed).  Each checks what its kernels
 // need and returns -1 for any other call; csrc/bindings.cpp (attn_route) picks the unit.
 int dl_attn_hd64_fwd(const DlAttn& a, hipStream_t st);
 int dl_attn_hd64_bwd(const DlAttn& a, hipStream_t st);
 int dl_attn_hd64q_fwd(const DlAttn& a, hipStream_t st);
 int dl_attn_hd64q_bwd(const DlAttn& a, hipStream_t st);
+int dl_attn_hd64qv_fwd(const DlAttn& a, hipStream_t st);
+int dl_attn_hd64qv_bwd(const DlAttn& a, hipStream_t st);
 int dl_attn_hd128_fwd(const DlAttn& a, hipStream_t st);
 int dl_attn_hd128_bwd(const DlAttn& a, hipStream_t st);
 

@@ -204,6 +204,12 @@ __device__ __forceinline__ void fwd_tiles(const KvRing& c, int kv_end, float sl2
 // past S are to the other forms: clamped loads, nothing written to lse / delta, no part in dK / dV
 // or the bias gradients.  Their out / dq rows are stored as zeros, not skipped: the compact buffers
 // go on into GEMMs (weight gradients sum over their rows), where unwritten memory must not appear.
+// Over packed keys (VARLEN and CQ: attention_varlen_compact_q.hip) sequence b's keys and values are
+// its slot of the packed buffer, B counts every sequence of seqinfo (the dummy tails too), and the
+// compact side stays rectangular: one Sq for all, which may exceed a short sequence's own slot (only
+// cnt[b] <= Sq and cnt[b] <= slot hold), so nothing below bounds a query row by S.  cnt[b] == 0 is
+// legal there (a dummy tail): its forward / dQ blocks store zeros and leave, its dK / dV blocks
+// write zeros to its slot of dkv.
 // The CQ instantiations take it as one more kernel argument (a parameter pack that is empty in the
 // other instantiations, so those keep their argument layout and their code).
 struct CompactQ {
@@ -245,10 +251,12 @@ __device__ __forceinline__ void zero_rows64(bf16_t* g, long ld, int rows) {
     for (int i = 0; i < 8; ++i) p[i] = make_uint4(0u, 0u, 0u, 0u);
   }
 }
-// live query rows of sequence b: the slot's count (CQ), else the sequence's rows
-template <bool CQ>
+// live query rows of sequence b: the slot's count (CQ), else the sequence's rows.  Over packed keys
+// (VARLEN and CQ) a count of 0 stays 0: the dummy tail sequences of a packed batch have no queries.
+template <bool VARLEN, bool CQ>
 __device__ __forceinline__ int q_rows(const CompactArg<CQ>& cq, int b, int S) {
-  if constexpr (CQ) return max(1, min(cq.cnt[b], cq.Sq));
+  if constexpr (CQ && VARLEN) return max(0, min(cq.cnt[b], cq.Sq));
+  else if constexpr (CQ) return max(1, min(cq.cnt[b], cq.Sq));
   else return S;
 }
 
@@ -268,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const bf16_t* __restri
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int S = seq_rows<VARLEN>(kvinfo, b, S_);
-  const int nq = q_rows<CQ>(cq, b, S);
+  const int nq = q_rows<VARLEN, CQ>(cq, b, S);
   if constexpr (VARLEN || CQ) {
     if (bid.x * (128 * QS) >= nq) {  // uniform over the block
       if constexpr (CQ) {  // a block of dead rows: zeros
@@ -350,7 +358,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dq_kernel(const bf16_t* __res
   const int b = bid.b, h = bid.h;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
   const int S = seq_rows<VARLEN>(kvinfo, b, S_);
-  const int nq = q_rows<CQ>(cq, b, S);
+  const int nq = q_rows<VARLEN, CQ>(cq, b, S);
   if constexpr (VARLEN || CQ) {
     if (bid.x * (128 * QS) >= nq) {  // uniform over the block
       if constexpr (CQ) {  // a block of dead rows: zeros
@@ -581,7 +589,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(
     if (bid.x * 128 >= S) return;  // uniform over the block
   }
   const long rb = seq_base<VARLEN>(kvinfo, b, S);
-  const int nq = q_rows<CQ>(cq, b, S);
+  const int nq = q_rows<VARLEN, CQ>(cq, b, S);
   const long qb = q_first<CQ>(cq, b, rb);
   const long ldq = CQ ? ldo : ld;
   const bf16_t* Qg = q_head<CQ>(cq, qkv, ld, ldo, rb, qb, h);
@@ -611,7 +619,9 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_dkdv_kernel(
   for (int u = 0; u < 1; ++u) k[u] = bid.x * 128 + w * 32 + 32 * u + r;
   bool use_len;
   const int kv_end = seq_kv_end<VARLEN>(kvinfo, B, b, S, use_len);
-  if (use_len && bid.x * 128 >= kv_end) {  // every key of this block is padding: dK = dV = 0
+  // every key of this block is padding, or (compact queries over packed keys) its sequence has no
+  // query at all: dK = dV = 0, written because dkv goes on into a GEMM that sums over every row
+  if ((use_len && bid.x * 128 >= kv_end) || (VARLEN && CQ && nq == 0)) {
 #pragma unroll
     for (int u = 0; u < 1; ++u) {
       if (k[u] < S) {
@@ -760,7 +770,7 @@ constexpr int kAttnXcd = 1;
 // measured: that this is why bits move with a kernel's address and with a row's 32-row sub-block.
 // docs/KERNELS.md ("Compact queries") has the listing; the pad is a change of its own, since it
 // changes output bits.
-#ifndef DL_ATTN_COMPACT_Q_UNIT
+#if !defined(DL_ATTN_COMPACT_Q_UNIT) && !defined(DL_ATTN_VARLEN_COMPACT_Q_UNIT)
 
 // This unit's kernels take the fused QKV buffer (no compact queries) at head_dim 64 with 16-byte
 // aligned rows, and S % 64 == 0 or the packed layout (the callers validate what seqinfo holds:
@@ -803,7 +813,7 @@ int dl_attn_hd64_bwd(const DlAttn& a, hipStream_t st) {
   return !a.seqinfo ? hd64_launch<false>(a, true, st) : hd64_launch<true>(a, true, st);
 }
 
-#else  // DL_ATTN_COMPACT_Q_UNIT
+#elif defined(DL_ATTN_COMPACT_Q_UNIT)
 
 // Compact queries (struct CompactQ above, DlAttn's compact block): head_dim 64 and the fixed-S
 // layout only; q / out rows of H*64 columns and key / value rows of 2*H*64, all 16-byte aligned
@@ -836,4 +846,41 @@ int dl_attn_hd64q_bwd(const DlAttn& a, hipStream_t st) {
   return 0;
 }
 
-#endif  // DL_ATTN_COMPACT_Q_UNIT
+#else  // DL_ATTN_VARLEN_COMPACT_Q_UNIT
+
+// Compact queries over packed keys and values (the VARLEN + CompactQ instantiations): head_dim 64;
+// kv is K's first column in the packed [T, ld] buffer, seqinfo / T / max_slot as in the packed form
+// (B counts the dummy tail sequences), q / out / dout / dq are [B*Sq, ldo] and lse / delta
+// [B, H, Sq].  Sq is not bounded by any slot; the callers validate what seqinfo holds.
+static bool hd64qv_ok(const DlAttn& a) {
+  return a.q && a.kv && a.qcnt && a.seqinfo && a.B >= 1 && a.H >= 1 && a.D == HD && a.T >= 64 && a.T % 64 == 0 &&
+         a.max_slot >= 64 && a.max_slot % 64 == 0 && a.max_slot <= a.T && a.Sq % 64 == 0 && a.Sq >= 64 &&
+         a.ld % 8 == 0 && a.ld >= 2L * a.H * HD && a.ldo % 8 == 0 && a.ldo >= (long)a.H * HD;
+}
+
+int dl_attn_hd64qv_fwd(const DlAttn& a, hipStream_t st) {
+  if (!hd64qv_ok(a)) return -1;
+  const CompactQ cq{a.q, nullptr, nullptr, 0, a.qcnt, a.Sq};
+  dim3 grid((a.Sq + 255) / 256, a.H, a.B);
+  attn_fwd_kernel<true, CompactQ><<<grid, 256, 0, st>>>(a.kv, a.ld, nullptr, a.seqinfo, a.out, a.ldo, a.lse, a.B, a.H,
+                                                        a.T, a.scale_log2(), kAttnXcd, cq);
+  return 0;
+}
+
+// The key blocks are sized by the largest slot, as in the packed form: a block past its sequence's
+// slot leaves at once, and the blocks of a sequence without queries only write zeros.
+int dl_attn_hd64qv_bwd(const DlAttn& a, hipStream_t st) {
+  if (!hd64qv_ok(a) || !a.dq || !a.dkv) return -1;
+  const float sl2 = a.scale_log2();
+  const CompactQ cq{a.q, a.dq, a.dkv, 2L * a.H * HD, a.qcnt, a.Sq};
+  dim3 grid_dq((a.Sq + 255) / 256, a.H, a.B), grid_kv((a.max_slot + 127) / 128, a.H, a.B);
+  attn_bwd_dq_kernel<true, CompactQ><<<grid_dq, 256, 0, st>>>(a.kv, a.ld, nullptr, a.seqinfo, a.out, a.dout, a.ldo,
+                                                              a.lse, a.delta, nullptr, a.dbias, a.B, a.H, a.T, sl2,
+                                                              a.scale, kAttnXcd, cq);
+  attn_bwd_dkdv_kernel<true, CompactQ><<<grid_kv, 256, 0, st>>>(a.kv, a.ld, nullptr, a.seqinfo, a.dout, a.ldo, a.lse,
+                                                                a.delta, nullptr, a.B, a.H, a.T, sl2, a.scale,
+                                                                kAttnXcd, cq);
+  return 0;
+}
+
+#endif  // translation unit

@@ -151,6 +151,12 @@ _SHARED_WGRAD = True
 # row): _AlbertLastLayerFn over ops.attn_fwd_q / attn_bwd_q.  Head_dim 64 on rectangular batches;
 # everything else, and every other model class, runs the full layer.
 _LAST_LAYER_ROWS = True
+# The same on packed batches (pack_sequences), over ops.attn_varlen_fwd_q / attn_varlen_bwd_q: the
+# compact queries of every sequence against its slot of the packed K / V.  Head_dim 64.  Opt-in: this
+# switch is what a call gets that does not say (forward / evaluate_batch ``last_layer_rows=None``, a
+# model whose ``packed_last_layer_rows`` attribute is None); run_trainer --packed_last_layer_rows
+# sets the attribute for the peer.
+_LAST_LAYER_ROWS_PACKED = False
 # AlbertForPreTraining's MLM loss on ops.mlm_cross_entropy: the tied decoder GEMM and the
 # cross-entropy in one set of kernels that keep the logits fp32 and never store them.  Embedding
 # size 128 only; a call that asks for the logits (return_logits) keeps the decoder GEMM.
@@ -206,6 +212,9 @@ class _AlbertLayerFn(torch.autograd.Function):
 class LastLayerRows:
     """The rows of the last layer's input that the heads read, in the compact layout of
     ``ops.attn_fwd_q``: sequence b owns a slot of ``Sq`` rows (a multiple of 64) of ``rows`` [B*Sq].
+    On a packed batch (``from_packed``, the layout of ``ops.attn_varlen_fwd_q``) ``rows`` index the
+    packed token buffer, B counts every sequence of ``seqinfo`` and a dummy tail sequence has
+    ``qcnt`` 0: all its places hold its first row and are dead.
     Its [CLS] row comes first.  Every other row sits in the half (rows 0-31 or 32-63) of a 64-row
     tile that it occupies in its own sequence, halves filled in order of appearance: the attention
     forward gives a query row the same bits wherever it sits only as long as it keeps its 32-row
@@ -223,9 +232,12 @@ class LastLayerRows:
         self.owner = owner
 
     @staticmethod
-    def _build(b_idx, s_pos, targets, B, Sp, Sq):
-        """b_idx / s_pos [N]: sequence and position of every MLM row, grouped by sequence."""
+    def _build(b_idx, s_pos, targets, base, total, Sq, n_real=None):
+        """b_idx / s_pos [N]: sequence and position of every MLM row, grouped by sequence.  base [B]:
+        the row of every sequence's first token in the layer's input of ``total`` rows; the first
+        ``n_real`` sequences (default: all) have a [CLS] row to read."""
         dev = b_idx.device
+        B = base.numel()
         # an entry at position 0 (a target on [CLS], or an unused entry of the fixed-shape form) shares
         # the [CLS] place: autograd then sums the heads' gradients of that row as it does on the full
         # output, before the layer's backward
@@ -246,11 +258,14 @@ class LastLayerRows:
         rank = torch.where(fits, rank, others + rank - cap)
         place = torch.where(cls, torch.zeros_like(rank), 64 * (rank // 32) + 32 * half + rank % 32)
         head_rows = b_idx * Sq + place
-        rows = (torch.arange(B, device=dev)[:, None] * Sp).expand(B, Sq).reshape(-1).clone()
-        rows[head_rows] = b_idx * Sp + s_pos
-        qcnt = torch.ones(B, dtype=torch.long, device=dev).scatter_reduce(0, b_idx, place + 1, "amax")
+        rows = base[:, None].expand(B, Sq).reshape(-1).clone()
+        rows[head_rows] = base[b_idx] + s_pos
+        qcnt = torch.ones(B, dtype=torch.long, device=dev)
+        if n_real is not None:
+            qcnt[n_real:] = 0
+        qcnt = qcnt.scatter_reduce(0, b_idx, place + 1, "amax")
         places = torch.arange(B * Sq, device=dev)
-        first = torch.full((B * Sp,), B * Sq, dtype=torch.long, device=dev).scatter_reduce(0, rows, places, "amin")
+        first = torch.full((total,), B * Sq, dtype=torch.long, device=dev).scatter_reduce(0, rows, places, "amin")
         return LastLayerRows(rows, qcnt.to(torch.int32), Sq, head_rows, targets, first[rows])
 
     @staticmethod
@@ -262,7 +277,8 @@ class LastLayerRows:
         if P == 0 or Sq >= Sp:
             return None
         b_idx = torch.arange(B, device=mlm_positions.device).repeat_interleave(P)
-        return LastLayerRows._build(b_idx, mlm_positions.reshape(-1), mlm_labels.reshape(-1), B, Sp, Sq)
+        base = torch.arange(B, device=mlm_positions.device) * Sp
+        return LastLayerRows._build(b_idx, mlm_positions.reshape(-1), mlm_labels.reshape(-1), base, B * Sp, Sq)
 
     @staticmethod
     def from_labels(labels, Sp):
@@ -276,12 +292,43 @@ class LastLayerRows:
         if M == 0 or Sq >= Sp:
             return None
         pos = torch.nonzero_static(sel.reshape(-1), size=M).squeeze(1)  # (b, position) order, no sync
-        return LastLayerRows._build(pos // S, pos % S, labels.reshape(-1)[pos], B, Sp, Sq)
+        base = torch.arange(B, device=labels.device) * Sp
+        return LastLayerRows._build(pos // S, pos % S, labels.reshape(-1)[pos], base, B * Sp, Sq)
+
+    @staticmethod
+    def from_packed(pk, mlm_positions=None, mlm_labels=None):
+        """The plan of a PackedBatch, from its packed labels (``pk.extras["labels"]`` [T]; the
+        per-sequence target counts are read on the host, the one synchronisation, as in
+        ``from_labels``) or from fixed-shape ``mlm_positions`` / ``mlm_labels`` [B, P] (none).  A
+        row's position inside its own sequence decides its half, and slots start on multiples of 64.
+        One Sq for all sequences: it may exceed a short sequence's slot.  None without any target or
+        when the compact buffer would not be smaller than the packed one."""
+        dev = pk.seqinfo.device
+        offs = pk.seqinfo[:pk.n_seq + 1].to(torch.long)
+        if mlm_positions is not None:
+            P = mlm_positions.shape[1]
+            Sq = (1 + P + 63) // 64 * 64
+            if P == 0 or pk.n_seq * Sq >= pk.T:
+                return None
+            b_idx = torch.arange(pk.B, device=dev).repeat_interleave(P)
+            s_pos, targets = mlm_positions.reshape(-1), mlm_labels.reshape(-1)
+        else:
+            lab = pk.extras["labels"]
+            cs = F.pad((lab != -100).cumsum(0), (1, 0))
+            host = (cs[offs[1:pk.B + 1]] - cs[offs[:pk.B]]).tolist()
+            M, Sq = sum(host), (1 + max(host) + 63) // 64 * 64
+            if M == 0 or pk.n_seq * Sq >= pk.T:
+                return None
+            t = torch.nonzero_static(lab != -100, size=M).squeeze(1)  # (b, position) order, no sync
+            b_idx = torch.bucketize(t, offs[1:pk.B + 1], right=True)
+            s_pos, targets = t - offs[b_idx], lab[t]
+        return LastLayerRows._build(b_idx, s_pos, targets, offs[:-1], pk.T, Sq, n_real=pk.B)
 
 
 class _AlbertLastLayerFn(torch.autograd.Function):
     """The last application of the shared layer, computed for the rows in ``sel`` (LastLayerRows)
-    only: [B*S, hidden] in, [B*Sq, hidden] out.  K and V are projected for every row, everything
+    only: [B*S, hidden] in, [B*Sq, hidden] out (with a PackedBatch as ``mask``: [T, hidden] in,
+    [n_seq*Sq, hidden] out).  K and V are projected for every row, everything
     else — Q, the attention queries, the output projection, both LayerNorms and the FFN — for the
     compact rows, forward and backward.  Same kernels and the same hand schedule as _AlbertLayerFn;
     each live output row equals the full layer's row."""
@@ -290,12 +337,15 @@ class _AlbertLastLayerFn(torch.autograd.Function):
     def forward(ctx, h, mask, lv, H, S, eps, sel):
         O = ops.OPS
         Hd = h.shape[1]
-        mbias, kvinfo = mask
         scale = 1.0 / math.sqrt(Hd // H)
         kv = O.gemm(h, lv["wqkv"][Hd:], lv["bqkv32"][Hd:], None, False, True, 0)
         hq = h.index_select(0, sel.rows)
         q = O.gemm(hq, lv["wqkv"][:Hd], lv["bqkv32"][:Hd], None, False, True, 0)
-        att, lse = ops.attn_fwd_q(q, kv, sel.qcnt, mbias, H, S, scale, kvinfo)
+        if isinstance(mask, PackedBatch):  # compact queries against each sequence's slot of K / V
+            att, lse = ops.attn_varlen_fwd_q(q, kv, sel.qcnt, mask.seqinfo, mask.seqinfo_host, H, sel.Sq, scale)
+        else:
+            mbias, kvinfo = mask
+            att, lse = ops.attn_fwd_q(q, kv, sel.qcnt, mbias, H, S, scale, kvinfo)
         out, saved = _post_attention_fwd(O, att, hq, lv, eps)
         ctx.save_for_backward(h, hq, q, kv, att, lse, *saved)
         ctx.lv, ctx.mask, ctx.H, ctx.S, ctx.sel, ctx.scale = lv, mask, H, S, sel, scale
@@ -312,8 +362,12 @@ class _AlbertLastLayerFn(torch.autograd.Function):
         # straight into the fp32 gradient (it is the first backward call; the layer before it opens
         # the series).
         datt, ds1 = _post_attention_bwd(O, dy.contiguous(), att, saved, lv)
-        dq, dkv, _ = ops.attn_bwd_q(q, kv, sel.qcnt, ctx.mask[0], att, datt, lse, ctx.H, ctx.S, ctx.scale, ctx.mask[1],
-                                    lv["gbqkv"])
+        if isinstance(ctx.mask, PackedBatch):
+            dq, dkv, _ = ops.attn_varlen_bwd_q(q, kv, sel.qcnt, ctx.mask.seqinfo, ctx.mask.seqinfo_host, att, datt, lse,
+                                               ctx.H, sel.Sq, ctx.scale, lv["gbqkv"])
+        else:
+            dq, dkv, _ = ops.attn_bwd_q(q, kv, sel.qcnt, ctx.mask[0], att, datt, lse, ctx.H, ctx.S, ctx.scale,
+                                        ctx.mask[1], lv["gbqkv"])
         O.gemm_acc_f32(dq, hq, lv["gwqkv"][:Hd], True, False)
         O.gemm_acc_f32(dkv, h, lv["gwqkv"][Hd:], True, False)
         # Data gradient.  Every row gets its K / V part; a row the heads read gets, as in the full
@@ -405,6 +459,9 @@ class AlbertPreTrainedModel(nn.Module):
     # Run forward on a packed, padding-free token buffer (data/packing.py): set by the trainers'
     # --pack_sequences, or per call with forward(..., pack_sequences=True).  Off by default.
     pack_sequences = False
+    # On packed batches, whether AlbertForPreTraining runs its last layer on the rows its heads read;
+    # None: the module switch _LAST_LAYER_ROWS_PACKED.  forward(..., last_layer_rows=...) overrides it.
+    packed_last_layer_rows: Optional[bool] = None
 
     def __init__(self, config: AlbertConfig):
         super().__init__()
@@ -568,12 +625,17 @@ class AlbertPreTrainedModel(nn.Module):
             return _AlbertLastLayerFn.apply(h, mask, lv, c.num_attention_heads, S, c.layer_norm_eps, last_rows)
         return _AlbertLayerFn.apply(h, mask, lv, c.num_attention_heads, S, c.layer_norm_eps)
 
-    def last_layer_rows_supported(self) -> bool:
-        """Whether the last layer can run on compact rows (LastLayerRows): the module switch, one
-        layer per group application and head_dim 64 (the only head size with compact-query attention
-        kernels)."""
+    def last_layer_rows_supported(self, packed: bool = False, request: Optional[bool] = None) -> bool:
+        """Whether the last layer can run on compact rows (LastLayerRows): the module switch (for a
+        ``packed`` batch the call's ``request``, None meaning the model's ``packed_last_layer_rows``
+        and then _LAST_LAYER_ROWS_PACKED), one layer per group application and head_dim 64 (the only
+        head size with compact-query attention kernels)."""
         c = self.config
-        return _LAST_LAYER_ROWS and c.inner_group_num == 1 and c.hidden_size == 64 * c.num_attention_heads
+        on = _LAST_LAYER_ROWS
+        if packed:
+            on = self.packed_last_layer_rows if request is None else request
+            on = _LAST_LAYER_ROWS_PACKED if on is None else on
+        return bool(on) and c.inner_group_num == 1 and c.hidden_size == 64 * c.num_attention_heads
 
     def _packed(self, pack_sequences, input_ids, attention_mask, token_type_ids, lengths, labels=None):
         """The PackedBatch of this call, or None when the call runs on the rectangular layout."""
@@ -588,13 +650,13 @@ class AlbertPreTrainedModel(nn.Module):
                last_rows=None):
         """Returns (sequence_output [B*S', H] bf16, S') where S' is S padded to a multiple of 64; with
         ``packed`` the trunk runs on the packed token buffer and returns ([T, H] bf16, None).
-        Only when the caller passes ``last_rows`` (a LastLayerRows built for this S'; rectangular
-        batches, see ``last_layer_rows_supported``) does the last layer run on those rows alone: the
-        output is then the compact [B*Sq, H] tensor."""
+        Only when the caller passes ``last_rows`` (a LastLayerRows built for this S', or for this
+        PackedBatch; see ``last_layer_rows_supported``) does the last layer run on those rows alone:
+        the output is then the compact [B*Sq, H] (packed: [n_seq*Sq, H]) tensor."""
         assert self.flat is not None, "call model.materialize(device) first"
         c, f = self.config, self.flat
         if packed is not None:
-            return self._encode_packed(packed), None
+            return self._encode_packed(packed, last_rows), None
         B, S = input_ids.shape
         Sp = (S + 63) // 64 * 64
         if attention_mask is None:
@@ -624,7 +686,7 @@ class AlbertPreTrainedModel(nn.Module):
             eps=c.layer_norm_eps)
         return self._layers(x, mask, Sp, last_rows), Sp
 
-    def _encode_packed(self, packed: PackedBatch):
+    def _encode_packed(self, packed: PackedBatch, last_rows=None):
         c, f = self.config, self.flat
         assert packed.max_slot <= c.max_position_embeddings, "sequence longer than max_position_embeddings"
         D = c.hidden_size // c.num_attention_heads
@@ -640,7 +702,7 @@ class AlbertPreTrainedModel(nn.Module):
                    f.g(emb + "token_type_embeddings.weight"), f.g(emb + "LayerNorm.weight"),
                    f.g(emb + "LayerNorm.bias")),
             eps=c.layer_norm_eps)
-        return self._layers(x, packed, 0)
+        return self._layers(x, packed, 0, last_rows)
 
     def _layers(self, x, mask, Sp, last_rows=None):
         """Mapping-in GEMM and the shared layer group(s) over a [rows, E] embedding output; ``mask`` is
@@ -698,13 +760,22 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         return sd
 
     def _trunk(self, input_ids, attention_mask, token_type_ids, labels, mlm_positions, mlm_labels, pack_sequences,
-               lengths):
+               lengths, last_layer_rows=None):
         """Encoder pass of ``forward`` / ``evaluate_batch``: (h, S', PackedBatch or None, row0, sel),
         row0[b] the row of sequence b's first token in h.  With sel (a LastLayerRows) h is the last
-        layer's compact output, S' its slot length."""
+        layer's compact output, S' its slot length.  ``last_layer_rows`` decides for packed batches
+        only (``last_layer_rows_supported``)."""
         pk = self._packed(pack_sequences, input_ids, attention_mask, token_type_ids, lengths,
                           labels if mlm_positions is None else None)
         if pk is not None:
+            sel = None
+            has_targets = mlm_positions is not None or "labels" in pk.extras
+            if has_targets and self.last_layer_rows_supported(True, last_layer_rows):
+                sel = LastLayerRows.from_packed(pk, mlm_positions, mlm_labels)
+            if sel is not None:
+                # h holds n_seq slots of Sq compact rows: sequence b's [CLS] row at b * Sq
+                h, _ = self.encode(packed=pk, last_rows=sel)
+                return h, sel.Sq, pk, torch.arange(pk.B, device=h.device) * sel.Sq, sel
             h, _ = self.encode(packed=pk)
             return h, None, pk, pk.row_start, None  # (b, position) -> row0[b] + position
         sel = self._last_rows(input_ids, labels, mlm_positions, mlm_labels)
@@ -779,14 +850,15 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         s = "sop_classifier.classifier."
         return ops.linear(pooled, f.w(s + "weight"), f.w(s + "bias"), f.g(s + "weight"), f.g(s + "bias"))
 
-    def evaluate_batch(self, batch, lengths=None):
+    def evaluate_batch(self, batch, lengths=None, last_layer_rows: Optional[bool] = None):
         """Held-out statistics of one batch (a stream's ``next_batch()`` dict), forward only: eval mode
         and ``no_grad`` (the previous mode is restored), the encoder and head path of ``forward``
         (``pack_sequences`` and both MLM target forms included) ending in ``ops.eval_cross_entropy``
         (the MLM head, under ``_FUSED_MLM_EVAL``: ``ops.mlm_eval_cross_entropy``, without the [M, V] logits).
         No gradient buffer is written, no [M, V] gradient is made and no random generator is drawn
         from.  Returns device scalars: ``mlm_loss_sum``, ``mlm_count``, ``mlm_top1``, ``mlm_top5``,
-        ``sop_loss_sum``, ``sop_count``, ``sop_correct`` (sums and counts, so batches add up)."""
+        ``sop_loss_sum``, ``sop_count``, ``sop_correct`` (sums and counts, so batches add up).
+        ``last_layer_rows``: as in ``forward``."""
         was_training = self.training
         self.eval()
         try:
@@ -795,7 +867,8 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
                 B, S = ids.shape
                 labels, pos = batch.get("labels"), batch.get("mlm_positions")
                 h, Sp, pk, row0, sel = self._trunk(ids, batch.get("attention_mask"), batch.get("token_type_ids"),
-                                                   labels, pos, batch.get("mlm_labels"), None, lengths)
+                                                   labels, pos, batch.get("mlm_labels"), None, lengths,
+                                                   last_layer_rows)
                 rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, pos, batch.get("mlm_labels"), sel)
                 if rows is None:
                     raise ValueError("evaluate_batch needs MLM targets: labels or mlm_positions/mlm_labels")
@@ -813,7 +886,8 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
                 "sop_correct": sop["top1"]}
 
     def forward(self, input_ids, attention_mask=None, token_type_ids=None, labels=None, sentence_order_label=None,
-                mlm_positions=None, mlm_labels=None, return_logits=False, pack_sequences=None, lengths=None):
+                mlm_positions=None, mlm_labels=None, return_logits=False, pack_sequences=None, lengths=None,
+                last_layer_rows: Optional[bool] = None):
         """HF-compatible pre-training forward.
 
         MLM targets either as HF ``labels`` [B, S] (-100 = ignore) or as fixed-shape
@@ -823,10 +897,15 @@ class AlbertForPreTraining(AlbertPreTrainedModel):
         ``pack_sequences`` (default: the model's attribute) runs the same computation on the packed,
         padding-free token buffer; ``lengths`` are the rows' host-side lengths (without them one
         device synchronisation reads them from ``attention_mask``).  Inputs and ``out`` are unchanged.
+
+        ``last_layer_rows`` (packed batches, head_dim 64): True runs the last layer only on the rows
+        the two heads read, False on every row; None takes the model's ``packed_last_layer_rows``,
+        and when that is None too the module switch ``_LAST_LAYER_ROWS_PACKED`` (off).  Rectangular
+        batches follow ``_LAST_LAYER_ROWS`` whatever this says.
         """
         B, S = input_ids.shape
         h, Sp, pk, row0, sel = self._trunk(input_ids, attention_mask, token_type_ids, labels, mlm_positions, mlm_labels,
-                                           pack_sequences, lengths)
+                                           pack_sequences, lengths, last_layer_rows)
         out = {}
         # ---- MLM head on masked positions only
         rows, tgt = self._mlm_targets(pk, row0, S, Sp, labels, mlm_positions, mlm_labels, sel)

@@ -197,7 +197,7 @@ def attn_fwd_q(q, kv, qcnt, mbias, H, S, scale, kvinfo=None):
     Returns out [B*Sq, H*64] and lse [B, H, Sq]; slot rows past ``qcnt[b]`` are dead (zeros in out,
     nothing written to lse).  Each
     live row equals the same row of ``attn_fwd`` bit for bit.  Head_dim 64 only: there is no
-    head_dim-128, composed or packed form."""
+    head_dim-128 or composed form; packed batches: ``attn_varlen_fwd_q``."""
     return OPS.attn_fwd_q(q, kv, qcnt, mbias, H, S, scale, kvinfo)
 
 
@@ -220,6 +220,23 @@ def attn_varlen_fwd(qkv, packed, H, scale):
 
 def attn_varlen_bwd(qkv, packed, out, dout, lse, H, scale, dbias=None):
     return OPS.attn_varlen_bwd(qkv, packed.seqinfo, packed.seqinfo_host, out, dout, lse, H, scale, dbias)
+
+
+def attn_varlen_fwd_q(q, kv, qcnt, seqinfo, seqinfo_host, H, Sq, scale):
+    """Fused attention of compact queries over a packed batch: ``kv`` [T, 2*H*64] (K | V; a column
+    slice of the packed QKV buffer will do) in the layout of ``seqinfo`` / ``seqinfo_host``, ``q``
+    [n*Sq, H*64] with sequence b's queries in the first ``qcnt[b]`` rows of its slot of ``Sq`` rows,
+    for all n sequences of ``seqinfo`` (the dummy tails too: ``qcnt`` 0).  ``Sq`` is a multiple of 64
+    and may exceed a sequence's own slot; ``qcnt[b] <= min(Sq, slot b)``.  Returns out [n*Sq, H*64]
+    and lse [n, H, Sq]; dead slot rows are zeros in out and unwritten in lse.  Head_dim 64 only."""
+    return OPS.attn_varlen_fwd_q(q, kv, qcnt, seqinfo, seqinfo_host, H, Sq, scale)
+
+
+def attn_varlen_bwd_q(q, kv, qcnt, seqinfo, seqinfo_host, out, dout, lse, H, Sq, scale, dbias=None):
+    """Backward of ``attn_varlen_fwd_q``: (dq [n*Sq, H*64], dkv [T, 2*H*64] for every row of the packed
+    buffer, delta [n, H, Sq]).  dkv is exactly zero past each key length and in every row of a
+    sequence with ``qcnt`` 0; the fused bias gradient in ``dbias`` (fp32 [3*H*64]) counts live rows."""
+    return OPS.attn_varlen_bwd_q(q, kv, qcnt, seqinfo, seqinfo_host, out, dout, lse, H, Sq, scale, dbias)
 
 
 class _Attention(torch.autograd.Function):

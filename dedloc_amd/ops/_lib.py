@@ -60,6 +60,10 @@ _SCHEMAS = [
     "attn_varlen_fwd(Tensor qkv, Tensor seqinfo, Tensor seqinfo_host, int H, float scale) -> (Tensor, Tensor)",
     "attn_varlen_bwd(Tensor qkv, Tensor seqinfo, Tensor seqinfo_host, Tensor out, Tensor dout, Tensor lse, int H, "
     "float scale, Tensor(a!)? dbias=None) -> Tensor",
+    "attn_varlen_fwd_q(Tensor q, Tensor kv, Tensor qcnt, Tensor seqinfo, Tensor seqinfo_host, int H, int Sq, "
+    "float scale) -> (Tensor, Tensor)",
+    "attn_varlen_bwd_q(Tensor q, Tensor kv, Tensor qcnt, Tensor seqinfo, Tensor seqinfo_host, Tensor out, Tensor dout, "
+    "Tensor lse, int H, int Sq, float scale, Tensor(a!)? dbias=None) -> (Tensor, Tensor, Tensor)",
     "embed_ln_pos_fwd(Tensor ids, Tensor? tt, Tensor pos, Tensor wemb, Tensor pemb, Tensor temb, Tensor gamma, Tensor beta, float eps) -> (Tensor, Tensor, Tensor, Tensor)",
     "embed_pos_bwd(Tensor ds, Tensor ids, Tensor? tt, Tensor pos, Tensor(a!) dwemb, Tensor(b!) dpemb, Tensor(c!) dtemb) -> ()",
     "attn_softmax_fwd(Tensor s, Tensor? mbias, int H, float c) -> (Tensor, Tensor)",
@@ -812,6 +816,78 @@ def _attn_varlen_bwd_cpu(qkv, seqinfo, seqinfo_host, out, dout, lse, H, scale, d
         g[r0:r1] = _attn_bwd_cpu(qkv[r0:r1], _slot_mbias(r1 - r0, n), out[r0:r1], dout[r0:r1], None, H, r1 - r0,
                                  scale, None, dbias)
     return g
+
+
+def _varlen_compact_q_slots(q, kv, qcnt, seqinfo_host, H, Sq, scale, what):
+    """Contract of the compact queries over a packed batch; (n, D, per sequence (b, r0, r1, live rows,
+    fp32 queries [H, Sq, D], keys and values [H, slot, D], scores [H, Sq, slot] with the keys past the
+    length masked))."""
+    T, D = kv.shape[0], kv.shape[1] // (2 * H)
+    if D != 64 or kv.shape[1] != 2 * H * D:
+        raise RuntimeError(f"dedloc_amd: {what}: compact queries exist for head_dim 64 only (got head_dim {D})")
+    rows, lens = packed_layout(seqinfo_host, T)
+    n = len(lens)
+    if Sq < 64 or Sq % 64:
+        raise RuntimeError(f"{what}: the query slot Sq = {Sq} must be a positive multiple of 64")
+    if tuple(q.shape) != (n * Sq, H * D) or qcnt.numel() != n:
+        raise RuntimeError(f"{what}: q must be [n*Sq, H*D] and qcnt int32[n] for the {n} sequences of seqinfo")
+    cnt = qcnt.clamp(0, Sq).tolist()
+    slots = []
+    for b in range(n):
+        r0, r1 = rows[b], rows[b + 1]
+        x = kv[r0:r1].float().reshape(r1 - r0, 2, H, D)
+        k, v = x[:, 0].transpose(0, 1), x[:, 1].transpose(0, 1)
+        qq = q[b * Sq:(b + 1) * Sq].float().reshape(Sq, H, D).transpose(0, 1)
+        sc = torch.matmul(qq, k.transpose(-1, -2)) * scale + _slot_mbias(r1 - r0, lens[b])
+        slots.append((b, r0, r1, torch.arange(Sq) < cnt[b], qq, k, v, sc))
+    return n, D, slots
+
+
+@_impl("attn_varlen_fwd_q")
+def _attn_varlen_fwd_q_cpu(q, kv, qcnt, seqinfo, seqinfo_host, H, Sq, scale):
+    """Attention of compact queries over a packed batch: sequence b (of the n of seqinfo, dummy tails
+    included) has its queries in the first qcnt[b] rows of slot b of q [n*Sq, H*D] and its keys /
+    values in its slot of kv [T, 2*H*D].  out [n*Sq, H*D], lse [n, H, Sq] (log2 units); rows past
+    qcnt[b] (all of them when it is 0) are dead: zeros in out, lse unwritten by the kernels, zero here."""
+    n, D, slots = _varlen_compact_q_slots(q, kv, qcnt, seqinfo_host, H, Sq, scale, "attn_varlen_fwd_q")
+    out = torch.zeros(n * Sq, H * D)
+    lse = torch.zeros(n, H, Sq)
+    for b, r0, r1, live, qq, k, v, sc in slots:
+        o = torch.matmul(torch.softmax(sc, -1), v).transpose(0, 1).reshape(Sq, H * D)
+        out[b * Sq:(b + 1) * Sq] = torch.where(live[:, None], o, torch.zeros_like(o))
+        l = torch.logsumexp(sc, -1) * math.log2(math.e)
+        lse[b] = torch.where(live[None, :], l, torch.zeros_like(l))
+    return out.to(q.dtype), lse  # bf16 storage; fp32 copies of q / kv give the plain fp32 reference
+
+
+@_impl("attn_varlen_bwd_q")
+def _attn_varlen_bwd_q_cpu(q, kv, qcnt, seqinfo, seqinfo_host, out, dout, lse, H, Sq, scale, dbias=None):
+    """Backward of ``attn_varlen_fwd_q``: (dq [n*Sq, H*D], dkv [T, 2*H*D] = dK | dV for every row of the
+    packed buffer, delta [n, H, Sq]); dead rows give nothing to dkv or to the bias gradient, and the
+    dkv rows of a sequence without queries, like those past a key length, are zero."""
+    n, D, slots = _varlen_compact_q_slots(q, kv, qcnt, seqinfo_host, H, Sq, scale, "attn_varlen_bwd_q")
+    HD = H * D
+    dq = torch.zeros(n * Sq, HD)
+    dkv = torch.zeros(kv.shape[0], 2 * HD)
+    delta = torch.zeros(n, H, Sq)
+    for b, r0, r1, live, qq, k, v, sc in slots:
+        lv = live[None, :, None].float()
+        p = torch.softmax(sc, -1) * lv
+        do = dout[b * Sq:(b + 1) * Sq].float().reshape(Sq, H, D).transpose(0, 1) * lv
+        o = out[b * Sq:(b + 1) * Sq].float().reshape(Sq, H, D).transpose(0, 1) * lv
+        dlt = (do * o).sum(-1, keepdim=True)
+        ds = p * (torch.matmul(do, v.transpose(-1, -2)) - dlt)
+        dq[b * Sq:(b + 1) * Sq] = (torch.matmul(ds, k) * scale).transpose(0, 1).reshape(Sq, HD)
+        dk = torch.matmul(ds.transpose(-1, -2), qq) * scale
+        dv = torch.matmul(p.transpose(-1, -2), do)
+        dkv[r0:r1] = torch.stack([dk, dv], dim=0).permute(2, 0, 1, 3).reshape(r1 - r0, 2 * HD)  # 2,H,slot,D
+        delta[b] = dlt.squeeze(-1)
+        if dbias is not None:  # value: colsum(dout), live rows only
+            dbias[2 * HD:] += do.transpose(0, 1).reshape(-1, HD).sum(0)
+    dq = dq.to(q.dtype)
+    if dbias is not None:  # query: colsum(dQ) as stored; key: 0
+        dbias[:HD] += dq.float().sum(0)
+    return dq, dkv.to(kv.dtype), delta
 
 
 def _softmax_logits(s, mbias, H, c):

@@ -117,6 +117,8 @@ class AlbertPeer:
             self.model.materialize(self.device)
             self.model.train()
             self.model.pack_sequences = bool(getattr(training_args, "pack_sequences", False))
+            if getattr(training_args, "packed_last_layer_rows", False):
+                self.model.packed_last_layer_rows = True
             self.opt, self.scheduler = build_optimizer(self.model, training_args)
         ca = collab_args
         validators, self.local_public_key = make_validators(ca.experiment_prefix)
