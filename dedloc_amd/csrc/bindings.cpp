@@ -1629,9 +1629,9 @@ inline int64_t conv_out(int64_t n, int64_t k, int64_t stride, int64_t pad) { ret
 struct StemCols {
   int64_t SCp, Kp;
 };
-inline StemCols stem_cols(int64_t R, int64_t S, int64_t C, bool lt) {
-  const int64_t SCp = (S * C + 7) / 8 * 8;  // hipBLASLt needs 16-byte rows only; conv.hip a multiple of BK
-  return {SCp, lt ? R * SCp : (R * SCp + 63) / 64 * 64};
+inline StemCols stem_cols(int64_t R, int64_t S, int64_t C) {
+  const int64_t SCp = (S * C + 7) / 8 * 8;
+  return {SCp, (R * SCp + 63) / 64 * 64};  // conv.hip takes a multiple of its 64-deep k-step
 }
 // The 7x7 stride-2 pad-3 stem over 3 channels (even H, W) runs as a 4x4 stride-1 conv over the
 // space-to-depth image xs [N, H/2, W/2, 16] (dl_stem_s2d): tap (tr, ts) and xs channel
@@ -1680,7 +1680,6 @@ inline at::Tensor stem_im2col(const at::Tensor& x, int64_t R, int64_t S, int64_t
 // with the KRSC weight as a K-outer operand) and the stem's column-matrix GEMM; their
 // weight gradients use gemm8's split-K slabs where both channel counts are multiples of 256 and the
 // implicit-GEMM conv.hip wgrad otherwise.
-constexpr bool conv_gemm() { return true; }
 inline bool is_pointwise(int64_t R, int64_t S, int64_t stride, int64_t pad) {
   return R == 1 && S == 1 && stride == 1 && pad == 0;
 }
@@ -1705,6 +1704,48 @@ inline DlConvGeom geom(const bf16_t* img, int64_t N, int64_t H, int64_t W, int64
                        int64_t dws) {
   return DlConvGeom{img, (int)N, (int)H, (int)W, (int)C, (int)I, (int)J, (int)sh, (int)sw,
                     (int)TR, (int)TS, (int)dh0, (int)dhs, (int)dw0, (int)dws};
+}
+
+// The operand conv.hip gathers for a conv over x: the forward and the weight gradient lower a conv
+// the same way, so a kept `cols` matrix means the same to both.
+enum class ConvOperand {
+  kDirect,   // Cin a multiple of 64: x itself, NHWC
+  kStemS2d,  // the 7x7 stride-2 stem: its space-to-depth image (stem_s2d_ok)
+  kColumns,  // other small-channel convs: an explicit im2col matrix (stem_cols), as a 1x1 conv over it
+};
+inline ConvOperand conv_operand(const at::Tensor& x, int64_t R, int64_t S, int64_t stride, int64_t pad) {
+  if (x.size(1) % 64 == 0) return ConvOperand::kDirect;
+  return stem_s2d_ok(x.size(1), R, S, stride, pad, x.size(2), x.size(3)) ? ConvOperand::kStemS2d : ConvOperand::kColumns;
+}
+struct ConvLowering {
+  ConvOperand kind;
+  DlConvGeom g;
+  at::Tensor keep;  // what g.img points into: alive until the launch
+  int64_t ldw;      // row length of the weight matrix that matches g
+  StemCols sc;      // kColumns: the column matrix's padding
+};
+// cols (optional): the operand that im2col_stem made for this input (ignored by kDirect)
+ConvLowering conv_lower(const at::Tensor& x, int64_t R, int64_t S, int64_t stride, int64_t pad, int64_t P, int64_t Q,
+                        const c10::optional<at::Tensor>& cols) {
+  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const ConvOperand kind = conv_operand(x, R, S, stride, pad);
+  if (kind == ConvOperand::kDirect)
+    return {kind, geom(cbf(x), N, H, W, C, P, Q, stride, stride, R, S, -pad, 1, -pad, 1), x, R * S * C, {}};
+  const bool s2d = kind == ConvOperand::kStemS2d;
+  const StemCols sc = s2d ? StemCols{} : stem_cols(R, S, C);
+  at::Tensor m;
+  if (cols.has_value()) {
+    TORCH_CHECK(cols->scalar_type() == at::kBFloat16 && cols->is_contiguous() && cols->dim() == 2 &&
+                    cols->size(0) == N * P * Q && cols->size(1) == (s2d ? 16 : sc.Kp),
+                "cols must be the stem's im2col_stem ", s2d ? "(space-to-depth) " : "", "matrix for this input");
+    m = *cols;
+  } else {
+    m = s2d ? stem_s2d(x) : stem_im2col(x, R, S, stride, pad, P, Q, sc);
+  }
+  // the 4x4 stride-1 conv over the space-to-depth image (see stem_s2d_ok)
+  if (s2d) return {kind, geom(cbf(m), N, H / 2, W / 2, 16, P, Q, 1, 1, 4, 4, -2, 1, -2, 1), m, 256, sc};
+  // a 1x1 conv over the column matrix as an [N*P*Q, 1, 1, Kp] "image"
+  return {kind, geom(cbf(m), N * P * Q, 1, 1, sc.Kp, 1, 1, 1, 1, 1, 1, 0, 1, 0, 1), m, sc.Kp, sc};
 }
 
 // stats (optional, fp32 [groups][2 Cout], accumulated): the BatchNorm statistics of the output per
@@ -1740,16 +1781,7 @@ at::Tensor im2col_stem(const at::Tensor& x, int64_t R, int64_t S, int64_t stride
   expect_nhwc(x, "x");
   if (stem_s2d_ok(x.size(1), R, S, stride, pad, x.size(2), x.size(3))) return stem_s2d(x);
   const int64_t P = conv_out(x.size(2), R, stride, pad), Q = conv_out(x.size(3), S, stride, pad);
-  return stem_im2col(x, R, S, stride, pad, P, Q, stem_cols(R, S, x.size(1), false));
-}
-
-inline at::Tensor stem_cols_checked(const c10::optional<at::Tensor>& cols, const at::Tensor& x, int64_t R, int64_t S,
-                                    int64_t stride, int64_t pad, int64_t P, int64_t Q, const StemCols& sc) {
-  if (!cols.has_value()) return stem_im2col(x, R, S, stride, pad, P, Q, sc);
-  TORCH_CHECK(cols->scalar_type() == at::kBFloat16 && cols->is_contiguous() && cols->dim() == 2 &&
-                  cols->size(0) == x.size(0) * P * Q && cols->size(1) == sc.Kp,
-              "cols must be the stem's im2col_stem matrix for this input");
-  return *cols;
+  return stem_im2col(x, R, S, stride, pad, P, Q, stem_cols(R, S, x.size(1)));
 }
 
 // fp32 zeros / ones [2, C] per device: the mean / rstd with which dl_bn_apply computes
@@ -1776,6 +1808,32 @@ inline at::Tensor affine_pass(const at::Tensor& c, const ConvAffine& af) {
   return y;
 }
 
+// y = the conv of a lowered operand with its weight matrix wm [K, lo.ldw] on conv.hip: with the
+// inference epilogue (af), or with the statistics epilogue where the kernel takes stat_rows, else the
+// plain kernel and one statistics pass.  False, with nothing launched, for a call conv.hip declines.
+bool conv_fwd_store(const ConvLowering& lo, const at::Tensor& wm, at::Tensor& y, float* stats, long stat_rows,
+                    int64_t groups, const ConvAffine* af) {
+  const int64_t K = y.size(1);
+  const hipStream_t st = cur_stream(y);
+  DlConvFwdJob job{lo.g, cbf(wm), lo.ldw, 0, 0, 0};
+  DlConvFwd d;
+  d.jobs = &job, d.njobs = 1;
+  d.N = (int)K;
+  d.out = bf(y), d.OH = lo.g.I, d.OW = lo.g.J, d.ldo = K;  // dense: one output pixel per GEMM row
+  if (af) {
+    d.scale = af->scale, d.shift = af->shift, d.res = af->res, d.relu = af->relu;
+    return dl_conv_fwd(d, st) == 0;
+  }
+  if (stats) {
+    job.stat_rows = stat_rows, d.stats = stats;
+    if (dl_conv_fwd(d, st) == 0) return true;
+    job.stat_rows = 0, d.stats = nullptr;
+  }
+  if (dl_conv_fwd(d, st) != 0) return false;
+  if (stats) check(dl_bn_stats(cbf(y), stats, stat_rows, (int)K, (int)groups, st), "bn_stats");
+  return true;
+}
+
 at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t stride, int64_t pad, float* stats,
                            int64_t groups, const c10::optional<at::Tensor>& cols, const ConvAffine* af) {
   expect_nhwc(x, "x");
@@ -1787,7 +1845,7 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
   auto y = at::empty({N, K, P, Q}, x.options(), at::MemoryFormat::ChannelsLast);
   const at::Tensor wk = krsc_view(w);
   const long stat_rows = N / groups * P * Q;  // output rows per statistics group
-  if (is_pointwise(R, S, stride, pad) && conv_gemm() && !(K <= narrow_1x1_max() && C % 64 == 0) &&
+  if (is_pointwise(R, S, stride, pad) && !(K <= narrow_1x1_max() && C % 64 == 0) &&
       !(C % 64 == 0 && few_tile_gemm(N * P * Q, K))) {
     const at::Tensor xr = rows2d(x), wr = wk.view({K, C});
     const DlGemm g = gemm_desc(xr, false, wr, true, bf(y), K);  // y[M, K] = x[M, C] w[K, C]^T
@@ -1795,78 +1853,29 @@ at::Tensor conv2d_fwd_impl(const at::Tensor& x, const at::Tensor& w, int64_t str
     else gemm_store(g, xr, cur_stream(x));
     return af ? affine_pass(y, *af) : y;
   }
-  if (C % 64 == 0) {
-    // conv.hip's epilogue stores whole 8-channel chunks (16 bytes); nothing launches otherwise
-    TORCH_CHECK(K % 8 == 0, "conv2d_fwd: Cout must be a multiple of 8 (got ", K, ")");
-    const DlConvGeom gm = geom(cbf(x), N, H, W, C, P, Q, stride, stride, R, S, -pad, 1, -pad, 1);
-    if (af) {
-      check(dl_conv_fwd_affine(gm, cbf(wk), R * S * C, (int)K, bf(y), (int)P, (int)Q, K, af->scale, af->shift, af->res,
-                               af->relu, cur_stream(x)),
-            "conv2d_bn_act");
-      return y;
-    }
-    if (stats && dl_conv_fwd(gm, cbf(wk), R * S * C, (int)K, bf(y), (int)P, (int)Q, 1, 1, 0, 0, K, cur_stream(x),
-                             stats, stat_rows) == 0)
-      return y;
-    check(dl_conv_fwd(gm, cbf(wk), R * S * C, (int)K, bf(y), (int)P, (int)Q, 1, 1, 0, 0, K, cur_stream(x)),
-          "conv2d_fwd");
-    if (stats) check(dl_bn_stats(cbf(y), stats, stat_rows, (int)K, (int)groups, cur_stream(x)), "bn_stats");
-    return y;
+  const ConvOperand kind = conv_operand(x, R, S, stride, pad);
+  const char* tag = kind == ConvOperand::kDirect ? "" : "(stem)";
+  // conv.hip's epilogue stores whole 8-channel chunks (16 bytes); nothing launches otherwise (the
+  // column matrix can still go to the tiled GEMM kernels)
+  TORCH_CHECK(kind == ConvOperand::kColumns || K % 8 == 0, "conv2d_fwd", tag, ": Cout must be a multiple of 8 (got ", K,
+              ")");
+  const ConvLowering lo = conv_lower(x, R, S, stride, pad, P, Q, cols);
+  at::Tensor wm = wk;  // [K, lo.ldw]: the weight with the operand's column order
+  if (kind == ConvOperand::kStemS2d) {
+    wm = at::zeros({K, 256}, w.options());
+    wm.index_copy_(1, stem_s2d_index(w.device()), wk.reshape({K, 147}));
+  } else if (kind == ConvOperand::kColumns) {  // rows padded as the column matrix's
+    wm = at::zeros({K, lo.sc.Kp}, w.options());
+    wm.narrow(1, 0, R * lo.sc.SCp).view({K, R, lo.sc.SCp}).narrow(2, 0, S * C).copy_(wk.reshape({K, R, S * C}));
   }
-  if (stem_s2d_ok(C, R, S, stride, pad, H, W)) {
-    TORCH_CHECK(K % 8 == 0, "conv2d_fwd(stem): Cout must be a multiple of 8 (got ", K, ")");
-    at::Tensor xs;
-    if (cols.has_value()) {
-      TORCH_CHECK(cols->scalar_type() == at::kBFloat16 && cols->is_contiguous() && cols->dim() == 2 &&
-                      cols->size(0) == N * P * Q && cols->size(1) == 16,
-                  "cols must be the stem's im2col_stem (space-to-depth) matrix for this input");
-      xs = *cols;
-    } else {
-      xs = stem_s2d(x);
-    }
-    auto w2 = at::zeros({K, 256}, w.options());
-    w2.index_copy_(1, stem_s2d_index(w.device()), wk.reshape({K, 147}));
-    const DlConvGeom gs = geom(cbf(xs), N, H / 2, W / 2, 16, P, Q, 1, 1, 4, 4, -2, 1, -2, 1);
-    if (af) {
-      check(dl_conv_fwd_affine(gs, cbf(w2), 256, (int)K, bf(y), (int)P, (int)Q, K, af->scale, af->shift, af->res,
-                               af->relu, cur_stream(x)),
-            "conv2d_bn_act(stem)");
-      return y;
-    }
-    if (stats && dl_conv_fwd(gs, cbf(w2), 256, (int)K, bf(y), (int)P, (int)Q, 1, 1, 0, 0, K, cur_stream(x), stats,
-                             stat_rows) == 0)
-      return y;
-    check(dl_conv_fwd(gs, cbf(w2), 256, (int)K, bf(y), (int)P, (int)Q, 1, 1, 0, 0, K, cur_stream(x)),
-          "conv2d_fwd(stem)");
-    if (stats) check(dl_bn_stats(cbf(y), stats, stat_rows, (int)K, (int)groups, cur_stream(x)), "bn_stats");
-    return y;
-  }
-  // other small-channel convs: im2col into a column matrix padded to a multiple of 64 columns, then
-  // one GEMM against the equally padded weight rows
-  const StemCols sc = stem_cols(R, S, C, false);
-  const at::Tensor col = stem_cols_checked(cols, x, R, S, stride, pad, P, Q, sc);
-  auto wp = at::zeros({K, sc.Kp}, w.options());
-  wp.narrow(1, 0, R * sc.SCp).view({K, R, sc.SCp}).narrow(2, 0, S * C).copy_(wk.reshape({K, R, S * C}));
-  // the column-matrix GEMM as a 1x1 conv over the [N*P*Q, 1, 1, Kp] "image" on conv.hip (its
-  // 256x64 tiles for the 64 stem channels, with the statistics epilogue; +2% over the tiled GEMM
-  // kernels in round 3), the tiled GEMM kernels for a column width conv.hip does not take
-  const int64_t Mc = col.size(0);
-  if (sc.Kp % 64 == 0) {
-    const DlConvGeom gc = geom(cbf(col), Mc, 1, 1, sc.Kp, 1, 1, 1, 1, 1, 1, 0, 1, 0, 1);
-    if (af && dl_conv_fwd_affine(gc, cbf(wp), sc.Kp, (int)K, bf(y), 1, 1, K, af->scale, af->shift, af->res, af->relu,
-                                 cur_stream(x)) == 0)
-      return y;
-    if (stats && dl_conv_fwd(gc, cbf(wp), sc.Kp, (int)K, bf(y), 1, 1, 1, 1, 0, 0, K, cur_stream(x), stats,
-                             stat_rows) == 0)
-      return y;
-    if (dl_conv_fwd(gc, cbf(wp), sc.Kp, (int)K, bf(y), 1, 1, 1, 1, 0, 0, K, cur_stream(x)) == 0) {
-      if (stats) check(dl_bn_stats(cbf(y), stats, stat_rows, (int)K, (int)groups, cur_stream(x)), "bn_stats");
-      return y;
-    }
-  }
-  const DlGemm g = gemm_desc(col, false, wp, true, bf(y), K);
-  if (stats) gemm_store_stats(g, stats, stat_rows, col, cur_stream(x));
-  else gemm_store(g, col, cur_stream(x));
+  // the column-matrix GEMM runs on conv.hip too (its 256x64 tiles for the 64 stem channels, with the
+  // statistics epilogue; +2% over the tiled GEMM kernels in round 3); those take what it declines
+  if (conv_fwd_store(lo, wm, y, stats, stat_rows, groups, af)) return y;
+  TORCH_CHECK(kind == ConvOperand::kColumns, "dedloc_amd: unsupported shape for ", af ? "conv2d_bn_act" : "conv2d_fwd",
+              tag);
+  const DlGemm g = gemm_desc(lo.keep, false, wm, true, bf(y), K);
+  if (stats) gemm_store_stats(g, stats, stat_rows, lo.keep, cur_stream(x));
+  else gemm_store(g, lo.keep, cur_stream(x));
   return af ? affine_pass(y, *af) : y;
 }
 
@@ -2009,12 +2018,17 @@ bool conv_dgrad_classes(const at::Tensor& dy, const at::Tensor& wk, int64_t stri
   // 3x3 data gradients ran at half the forward's speed); per-class launches when the classes need
   // different kernel variants
   const hipStream_t st = cur_stream(dy);
-  if (!jobs.empty() && dl_conv_fwd_multi(jobs.data(), (int)jobs.size(), (int)C, bf(dx), (int)H, (int)W, (int)stride,
-                                         (int)stride, C, st, bn ? sums : nullptr, bn) != 0) {
-    for (const DlConvFwdJob& jb : jobs)
-      check(dl_conv_fwd(jb.g, jb.w, jb.ldw, (int)C, bf(dx), (int)H, (int)W, (int)stride, (int)stride, jb.oh0, jb.ow0, C,
-                        st, bn ? sums : nullptr, jb.stat_rows, bn),
-            "conv2d_dgrad");
+  DlConvFwd d;
+  d.jobs = jobs.data(), d.njobs = (int)jobs.size();
+  d.N = (int)C;
+  d.out = bf(dx), d.OH = (int)H, d.OW = (int)W, d.osh = d.osw = (int)stride, d.ldo = C;
+  d.stats = bn ? sums : nullptr, d.bn = bn;
+  if (!jobs.empty() && dl_conv_fwd(d, st) != 0) {
+    for (const DlConvFwdJob& jb : jobs) {
+      DlConvFwd one = d;
+      one.jobs = &jb, one.njobs = 1;
+      check(dl_conv_fwd(one, st), "conv2d_dgrad");
+    }
   }
   return true;
 }
@@ -2041,8 +2055,7 @@ at::Tensor conv2d_dgrad(const at::Tensor& dy_in, const at::Tensor& w, int64_t st
     TORCH_CHECK(residual->sizes() == dx.sizes(), "conv2d_dgrad: residual must have the input's shape");
   }
   const at::Tensor wk = krsc_view(w);  // [K, R, S, C]
-  if (is_pointwise(R, S, stride, pad) && H == P && W == Q && conv_gemm() &&
-      !(C <= narrow_1x1_max() && K % 64 == 0)) {
+  if (is_pointwise(R, S, stride, pad) && H == P && W == Q && !(C <= narrow_1x1_max() && K % 64 == 0)) {
     // dX[M, C] = dY[M, K] W[K, C] (+ residual): the weight as a K-outer B operand, no transposed copy
     const at::Tensor dyr = rows2d(dy), wkc = wk.view({K, C});
     DlGemm g = gemm_desc(dyr, false, wkc, false, bf(dx), C);
@@ -2088,7 +2101,7 @@ std::tuple<at::Tensor, bool> conv2d_dgrad_bn(const at::Tensor& dy, const at::Ten
   const at::Tensor gdy = dy.is_contiguous(at::MemoryFormat::ChannelsLast) ? dy
                                                                            : dy.contiguous(at::MemoryFormat::ChannelsLast);
   const int64_t K = w.size(0), R = w.size(2), S = w.size(3);
-  if (is_pointwise(R, S, stride, pad) && gdy.size(2) == H && gdy.size(3) == W && conv_gemm()) {
+  if (is_pointwise(R, S, stride, pad) && gdy.size(2) == H && gdy.size(3) == W) {
     expect_nhwc(gdy, "dy");
     if (residual.has_value()) {
       expect_nhwc(*residual, "residual");
@@ -2136,49 +2149,34 @@ void conv2d_wgrad(const at::Tensor& dy_in, const at::Tensor& x, at::Tensor dw, i
   expect_nhwc(dy, "dy");
   if (!cols.has_value()) expect_nhwc(x, "x");  // with the stem's cols only x's shape is read
   TORCH_CHECK(dw.is_cuda() && dw.scalar_type() == at::kFloat && dw.dim() == 4, "dw must be an fp32 4-D GPU tensor");
-  const int64_t N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
+  const int64_t C = x.size(1);
   const int64_t K = dy.size(1), P = dy.size(2), Q = dy.size(3), R = dw.size(2), S = dw.size(3);
   TORCH_CHECK(dw.size(0) == K && dw.size(1) == C, "conv2d_wgrad: dw shape mismatch");
   TORCH_CHECK(!cols.has_value() || C % 64 != 0, "conv2d_wgrad: cols are the stem's (C not a multiple of 64) only");
   at::Tensor dk = dw.permute({0, 2, 3, 1});  // [K, R, S, C]
   const bool direct = dk.is_contiguous();
   at::Tensor acc = direct ? dk : at::zeros({K, R, S, C}, dw.options());
-  int rc;
-  if (is_pointwise(R, S, stride, pad) && conv_gemm() && K % 256 == 0 && C % 256 == 0) {
+  if (is_pointwise(R, S, stride, pad) && K % 256 == 0 && C % 256 == 0) {
     gemm_acc_f32(rows2d(dy), rows2d(x), acc.view({K, C}), true, false);
-  } else if (C % 8 == 0 && C >= 8 && C % 64 == 0) {
-    const DlConvGeom gm = geom(cbf(x), N, H, W, C, P, Q, stride, stride, R, S, -pad, 1, -pad, 1);
-    // split partials accumulate with fp32 atomics (the slab-and-sum form measured no consistent
-    // gain in round 3 and was removed)
-    rc = dl_conv_wgrad(gm, cbf(dy), K, (int)K, f32(acc), R * S * C, (int)(R * S * C), cur_stream(dy));
-    check(rc, "conv2d_wgrad");
-  } else if (stem_s2d_ok(C, R, S, stride, pad, H, W)) {
-    // stem: 4x4 wgrad over the space-to-depth image into [K, 256], folded back onto the 7x7 taps
-    at::Tensor xs;
-    if (cols.has_value()) {
-      TORCH_CHECK(cols->scalar_type() == at::kBFloat16 && cols->is_contiguous() && cols->dim() == 2 &&
-                      cols->size(0) == N * P * Q && cols->size(1) == 16,
-                  "cols must be the stem's im2col_stem (space-to-depth) matrix for this input");
-      xs = *cols;
-    } else {
-      xs = stem_s2d(x);
-    }
-    auto slab = at::zeros({K, 256}, dw.options());
-    rc = dl_conv_wgrad(geom(cbf(xs), N, H / 2, W / 2, 16, P, Q, 1, 1, 4, 4, -2, 1, -2, 1), cbf(dy), K, (int)K,
-                       f32(slab), 256, 256, cur_stream(dy));
-    check(rc, "conv2d_wgrad(stem)");
-    acc.view({K, R * S * C}).add_(slab.index_select(1, stem_s2d_index(dw.device())));
   } else {
-    // other small-channel convs: wgrad over the padded column matrix into a [K, R, SCp] slab, then
-    // the real columns
-    const StemCols sc = stem_cols(R, S, C, false);
-    const int64_t M = N * P * Q;
-    const at::Tensor col = stem_cols_checked(cols, x, R, S, stride, pad, P, Q, sc);
-    auto slab = at::zeros({K, R, sc.SCp}, dw.options());
-    rc = dl_conv_wgrad(geom(cbf(col), M, 1, 1, sc.Kp, 1, 1, 1, 1, 1, 1, 0, 1, 0, 1), cbf(dy), K, (int)K,
-                       f32(slab), R * sc.SCp, (int)(R * sc.SCp), cur_stream(dy));
-    check(rc, "conv2d_wgrad(stem)");
-    acc.view({K, R, S * C}).add_(slab.narrow(2, 0, S * C));
+    // conv.hip over the forward's operand; split partials accumulate with fp32 atomics (the
+    // slab-and-sum form measured no consistent gain in round 3 and was removed)
+    const ConvLowering lo = conv_lower(x, R, S, stride, pad, P, Q, cols);
+    const hipStream_t st = cur_stream(dy);
+    if (lo.kind == ConvOperand::kDirect) {
+      check(dl_conv_wgrad(lo.g, cbf(dy), K, (int)K, f32(acc), lo.ldw, (int)lo.ldw, st), "conv2d_wgrad");
+    } else if (lo.kind == ConvOperand::kStemS2d) {
+      // into [K, 256], folded back onto the 7x7 taps
+      auto slab = at::zeros({K, 256}, dw.options());
+      check(dl_conv_wgrad(lo.g, cbf(dy), K, (int)K, f32(slab), 256, 256, st), "conv2d_wgrad(stem)");
+      acc.view({K, R * S * C}).add_(slab.index_select(1, stem_s2d_index(dw.device())));
+    } else {
+      // into a [K, R, SCp] slab (the column matrix's zero tail left out), then the real columns
+      const int64_t SCp = lo.sc.SCp;
+      auto slab = at::zeros({K, R, SCp}, dw.options());
+      check(dl_conv_wgrad(lo.g, cbf(dy), K, (int)K, f32(slab), R * SCp, (int)(R * SCp), st), "conv2d_wgrad(stem)");
+      acc.view({K, R, S * C}).add_(slab.narrow(2, 0, S * C));
+    }
   }
   if (!direct) dk.add_(acc);
 }

@@ -275,38 +275,37 @@ int dl_bn_bwd_prep(bf16_t* dy, const bf16_t* y, const bf16_t* x, const float* me
 
 // conv.hip — implicit-GEMM NHWC convolutions.  The gathered operand is an NHWC image
 // [Nimg, H, W, C]; GEMM rows m = (n, i, j) over [Nimg, I, J]; tap t = (tr < TR, ts < TS) reads
-// pixel (i*sh + dh0 + tr*dhs, j*sw + dw0 + ts*dws) (zero outside the image).
+// pixel (i*sh + dh0 + tr*dhs, j*sw + dw0 + ts*dws) (zero outside the image).  Every forward and
+// data-gradient call is one DlConvFwd descriptor given to dl_conv_fwd.
 struct DlConvGeom {
   const bf16_t* img;
   int Nimg, H, W, C;
   int I, J, sh, sw;
   int TR, TS, dh0, dhs, dw0, dws;
 };
-// out[(n, i*osh+oh0, j*osw+ow0), 0..N) (NHWC, row stride ldo) = sum_{t,c} img(pixel(m,t), c) * w[n][t*C + c]
-// stats (optional): BatchNorm statistics of the stored output as DL_EPI_STATS (stat_rows a
-// multiple of 128 dividing M; -1 otherwise)
-int dl_conv_fwd(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, int osh, int osw,
-                int oh0, int ow0, long ldo, hipStream_t st, float* stats = nullptr, long stat_rows = 0,
-                const DlBnBwdEpi* bn = nullptr);  // bn (needs stats): BN-backward preparation epilogue
-// dl_conv_fwd (dense output: stride-1 rows, row stride ldo) with a frozen BatchNorm in the epilogue:
-// out = bf16(act(fmaf(float(bf16(conv)), scale[ch], shift[ch]) [+ res])), scale / shift fp32 [N],
-// res (optional) in the output's layout, N a multiple of 8; no statistics
-int dl_conv_fwd_affine(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, long ldo,
-                       const float* scale, const float* shift, const bf16_t* res, int relu, hipStream_t st);
-// several independent forward jobs (same output tensor / channel count / epilogue, e.g. the parity
-// classes of a strided data gradient) in ONE launch; at most 4 jobs, all of one kernel variant
-// (-1 and nothing launched otherwise)
+// one job: out[(n, i*osh+oh0, j*osw+ow0), 0..N) (NHWC, row stride ldo) = sum_{t,c} img(pixel(m,t), c) * w[n][t*C + c]
 struct DlConvFwdJob {
   DlConvGeom g;
   const bf16_t* w;
   long ldw;
   int oh0, ow0;
-  long stat_rows;
+  long stat_rows;  // with stats: output rows per statistics group, a multiple of 128 dividing M
 };
-int dl_conv_fwd_multi(const DlConvFwdJob* jobs, int njobs, int N, bf16_t* out, int OH, int OW, int osh, int osw,
-                      long ldo, hipStream_t st, float* stats = nullptr, const DlBnBwdEpi* bn = nullptr);
-// dw[k][col] += sum_m dy[m][k] * img(pixel(m, col / C), col % C)    (fp32; col < Ncols; the pixel
-// reduction is split over workgroups that add their partial tiles with fp32 atomics)
+// One forward call.  Several jobs (same output tensor / channel count / epilogue, e.g. the parity
+// classes of a strided data gradient) run in ONE launch: at most 4 jobs, all of one kernel variant.
+struct DlConvFwd {
+  const DlConvFwdJob* jobs = nullptr; int njobs = 0;
+  int N = 0;  // output channels, a multiple of 8
+  bf16_t* out = nullptr; int OH = 0, OW = 0, osh = 1, osw = 1; long ldo = 0;
+  float* stats = nullptr;  // optional: BatchNorm statistics of the stored output as DL_EPI_STATS
+  const DlBnBwdEpi* bn = nullptr;  // optional (needs stats): BN-backward preparation epilogue
+  // optional inference epilogue (scale set: a frozen BatchNorm), for one job with a dense output (osh =
+  // osw = 1, oh0 = ow0 = 0), N >= 8 and no stats / bn: out = bf16(act(fmaf(float(bf16(conv)), scale[ch],
+  // shift[ch]) [+ res])), scale / shift fp32 [N], res (optional) in the output's layout
+  const float* scale = nullptr; const float* shift = nullptr; const bf16_t* res = nullptr; int relu = 0;
+};
+// -1 and nothing launched for a call the kernels do not take
+int dl_conv_fwd(const DlConvFwd& d, hipStream_t st);
 // dst[c][tr][ts][k] = src[k][r0 + tr*st][s0 + ts*st][c] for many (src KRSC bf16, K and C multiples of
 // 64): the tap-transposed data-gradient weights of several convs and parity classes in one launch
 struct DlWtJob {
@@ -316,11 +315,13 @@ struct DlWtJob {
   int r0, s0, st, TR, TS;
 };
 int dl_conv_dgrad_weights_batched(const DlWtJob* jobs, int njobs, hipStream_t st);
+// dw[k][col] += sum_m dy[m][k] * img(pixel(m, col / C), col % C)    (fp32; col < Ncols; the pixel
+// reduction is split over workgroups that add their partial tiles with fp32 atomics)
 int dl_conv_wgrad(const DlConvGeom& g, const bf16_t* dy, long ldy, int Cout, float* dw, long lddw, int Ncols,
                   hipStream_t st);
-// stem im2col: col[m][r*SCp + s*C + c] (filter rows padded to SCp columns), zero columns up to Kp
 // space-to-depth of the 3-channel stem input: x NHWC [N, H, W, 3] -> [N, H/2, W/2, 16] (H, W even)
 int dl_stem_s2d(const bf16_t* x, int N, int H, int W, bf16_t* xs, hipStream_t st);
+// stem im2col: col[m][r*SCp + s*C + c] (filter rows padded to SCp columns), zero columns up to Kp
 int dl_im2col(const bf16_t* x, int N, int H, int W, int C, int R, int S, int stride, int pad, int P, int Q, int SCp,
               int Kp, bf16_t* col, hipStream_t st);
 

@@ -959,31 +959,38 @@ __global__ __launch_bounds__(256) void wt_transpose_kernel(const WtJobs P) {
 #ifndef DL_CONV_FWD_WG
 #define DL_CONV_FWD_WG 1024  // (a measurement build may override)
 #endif
-int dl_conv_fwd_multi(const DlConvFwdJob* jobs, int njobs, int N, bf16_t* out, int OH, int OW, int osh, int osw,
-                      long ldo, hipStream_t st, float* stats, const DlBnBwdEpi* bn) {
+int dl_conv_fwd(const DlConvFwd& d, hipStream_t st) {
+  const int N = d.N;
+  // several jobs: one launch (stride-2 data gradients, SwAV b=64 shapes: 1022 -> 799 us per
+  // iteration over the 12 strided convs, every shape faster; profiles/r5_conv_dgrad_merged_classes.jsonl)
+  const bool multi = d.njobs > 1, aff = d.scale != nullptr;
   // the epilogue stores whole 8-channel chunks: a 4-channel tail would write into the next pixel
   // (past the tensor at the last one)
-  if (njobs < 1 || njobs > MAXJ || N % 8 || ldo % 8) return -1;
-  if (bn && (!stats || !bn->X || bn->ldx % 8 || (!bn->Y && (!bn->gamma || !bn->beta)))) return -1;
+  if (d.njobs < 1 || d.njobs > MAXJ || N % 8 || d.ldo % 8) return -1;
+  if (d.bn && (!d.stats || !d.bn->X || d.bn->ldx % 8 || (!d.bn->Y && (!d.bn->gamma || !d.bn->beta)))) return -1;
+  // the inference epilogue: one job, dense output, no statistics
+  if (aff && (multi || !d.shift || d.stats || d.bn || d.osh != 1 || d.osw != 1 || d.jobs[0].oh0 || d.jobs[0].ow0 ||
+              N < 8))
+    return -1;
   // validate every job before anything launches (-1: nothing ran); all jobs must take one variant
   int variant = -1;
   long tiles[MAXJ];
   long total = 0;
-  for (int c = 0; c < njobs; ++c) {
-    const DlConvGeom& g = jobs[c].g;
-    const long stat_rows = jobs[c].stat_rows;
+  for (int c = 0; c < d.njobs; ++c) {
+    const DlConvGeom& g = d.jobs[c].g;
+    const long stat_rows = d.jobs[c].stat_rows;
     const bool sub = g.C < BK;  // C in {8, 16, 32}: several taps per k-step (SUB kernels)
-    if ((sub ? (BK % g.C || g.C % 8) : g.C % BK) || jobs[c].ldw % 8 || g.I < 0 || g.J < 0) return -1;
-    if (sub && (bn || (g.TR * g.TS * g.C) % BK)) return -1;
+    if ((sub ? (BK % g.C || g.C % 8) : g.C % BK) || d.jobs[c].ldw % 8 || g.I < 0 || g.J < 0) return -1;
+    if (sub && (d.bn || (g.TR * g.TS * g.C) % BK)) return -1;
     const long M = (long)g.Nimg * g.I * g.J;
     // statistics: every 128-row tile inside one group, whole 8-channel chunks
-    if (stats && M > 0 && (stat_rows < BM || stat_rows % BM || M % stat_rows || N % 8)) return -1;
+    if (d.stats && M > 0 && (stat_rows < BM || stat_rows % BM || M % stat_rows || N % 8)) return -1;
     if (M >= (1L << 24)) return -1;  // fdiv exactness bound (pixel decodes)
-    const long img_bytes = 2L * g.Nimg * g.H * g.W * g.C, w_bytes = 2L * N * jobs[c].ldw;
+    const long img_bytes = 2L * g.Nimg * g.H * g.W * g.C, w_bytes = 2L * N * d.jobs[c].ldw;
     if (img_bytes >= (1L << 31) || w_bytes >= (1L << 31)) return -1;  // 32-bit buffer offsets
     // outputs of at most 64 channels: 256 x 64 tiles (the 128-wide channel tile would be half
     // empty; SwAV b=64 2015 / 2037 -> 2058 / 2055 samples/s in round 3)
-    const bool narrow = N <= 64 && (!stats || stat_rows % 256 == 0);
+    const bool narrow = N <= 64 && (!d.stats || stat_rows % 256 == 0);
     const int v = 2 * sub + narrow;
     tiles[c] = 0;
     if (M == 0 || N == 0) continue;
@@ -995,120 +1002,66 @@ int dl_conv_fwd_multi(const DlConvFwdJob* jobs, int njobs, int N, bf16_t* out, i
   }
   if (total == 0) return 0;
   if (total >= (1L << 31)) return -1;
-  // several jobs: one launch (stride-2 data gradients, SwAV b=64 shapes: 1022 -> 799 us per
-  // iteration over the 12 strided convs, every shape faster; profiles/r5_conv_dgrad_merged_classes.jsonl)
-  const bool multi = njobs > 1;
-  FwdMulti P{};
-  int wg = 0;
-  auto launch = [&]() {
-    const bool sub = variant & 2, narrow = variant & 1;
-    const int lds = 2 * ((narrow ? 256 : BM) + (narrow ? 64 : BN)) * 128;
-    const dim3 grid(wg);
-    if (multi) {
-      if (narrow) conv_fwd_kernel<256, 64, false, true><<<grid, NT, lds, st>>>(P);
-      else conv_fwd_kernel<BM, BN, false, true><<<grid, NT, lds, st>>>(P);
-    } else if (sub) {
-      if (narrow) conv_fwd_kernel<256, 64, true><<<grid, NT, lds, st>>>(P);
-      else conv_fwd_kernel<BM, BN, true><<<grid, NT, lds, st>>>(P);
-    } else {
-      if (narrow) conv_fwd_kernel<256, 64><<<grid, NT, lds, st>>>(P);
-      else conv_fwd_kernel<BM, BN><<<grid, NT, lds, st>>>(P);
-    }
-  };
+  const bool sub = variant & 2, narrow = variant & 1;
+  if (multi && sub) return -1;  // no SUB job-indexed kernel (data gradients have C >= 64)
+  constexpr int lds_wide = 2 * (BM + BN) * 128, lds_narrow = 2 * (256 + 64) * 128;
   static bool attr = false;
   if (!attr) {
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM + BN) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<256, 64>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM + BN) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<256, 64, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM + BN) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<256, 64, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128));
+    // (the device code holds the kernels in the order in which this file first names them)
+    const auto big_lds = [](const void* kern, int lds) {
+      DL_HIP_CHECK(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+    };
+    big_lds((const void*)conv_fwd_kernel<256, 64, false, true>, lds_narrow);
+    big_lds((const void*)conv_fwd_kernel<BM, BN, false, true>, lds_wide);
+    big_lds((const void*)conv_fwd_kernel<256, 64, true>, lds_narrow);
+    big_lds((const void*)conv_fwd_kernel<BM, BN, true>, lds_wide);
+    big_lds((const void*)conv_fwd_kernel<256, 64>, lds_narrow);
+    big_lds((const void*)conv_fwd_kernel<BM, BN>, lds_wide);
+    big_lds((const void*)conv_fwd_kernel<BM, BN, false, false, true>, lds_wide);
+    big_lds((const void*)conv_fwd_kernel<256, 64, false, false, true>, lds_narrow);
+    big_lds((const void*)conv_fwd_kernel<BM, BN, true, false, true>, lds_wide);
+    big_lds((const void*)conv_fwd_kernel<256, 64, true, false, true>, lds_narrow);
     attr = true;
   }
-  if (multi && (variant & 2)) return -1;  // no SUB job-indexed kernel (data gradients have C >= 64)
-  for (int c = 0; c < njobs; ++c) {
+  FwdAffine P{};  // the kernels without the inference epilogue take its FwdMulti part
+  int wg = 0;
+  for (int c = 0; c < d.njobs; ++c) {
     if (tiles[c] == 0) continue;
-    const DlConvFwdJob& jb = jobs[c];
+    const DlConvFwdJob& jb = d.jobs[c];
     // ~1024 workgroups (two per CU, two rounds); short-K shapes get several tiles per workgroup
     const int tpw = (int)std::max<long>(1, tiles[c] / DL_CONV_FWD_WG);
     const DlConvGeom& g = jb.g;
-    FwdArgs& a = P.a[P.n];
-    a = FwdArgs{g, jb.w, jb.ldw, N, out, OH, OW, osh, osw, jb.oh0, jb.ow0, ldo, g.Nimg * g.I * g.J, g.TR * g.TS * g.C,
-                (unsigned)(2L * g.Nimg * g.H * g.W * g.C), (unsigned)(2L * N * jb.ldw), tpw, stats, jb.stat_rows,
-                bn ? *bn : DlBnBwdEpi{}, bn ? 1 : 0};
+    P.a[P.n] = FwdArgs{g, jb.w, jb.ldw, N, d.out, d.OH, d.OW, d.osh, d.osw, jb.oh0, jb.ow0, d.ldo, g.Nimg * g.I * g.J,
+                       g.TR * g.TS * g.C, (unsigned)(2L * g.Nimg * g.H * g.W * g.C), (unsigned)(2L * N * jb.ldw), tpw,
+                       d.stats, jb.stat_rows, d.bn ? *d.bn : DlBnBwdEpi{}, d.bn ? 1 : 0};
     P.wg_begin[P.n++] = wg;
     const int jw = (int)((tiles[c] + tpw - 1) / tpw);
     wg += multi ? (jw + 7) / 8 * 8 : jw;  // surplus workgroups find no tile and return
     P.wg_begin[P.n] = wg;
-    if (!multi) {  // this job alone
-      launch();
-      P = FwdMulti{};
-      wg = 0;
+  }
+  P.scale = d.scale;
+  P.shift = d.shift;
+  P.res = d.res;
+  P.relu = d.relu;
+  const dim3 grid(wg);
+  const int lds = narrow ? lds_narrow : lds_wide;
+  if (multi) {
+    if (narrow) conv_fwd_kernel<256, 64, false, true><<<grid, NT, lds, st>>>(P);
+    else conv_fwd_kernel<BM, BN, false, true><<<grid, NT, lds, st>>>(P);
+  } else if (aff) {
+    if (sub) {
+      if (narrow) conv_fwd_kernel<256, 64, true, false, true><<<grid, NT, lds, st>>>(P);
+      else conv_fwd_kernel<BM, BN, true, false, true><<<grid, NT, lds, st>>>(P);
+    } else {
+      if (narrow) conv_fwd_kernel<256, 64, false, false, true><<<grid, NT, lds, st>>>(P);
+      else conv_fwd_kernel<BM, BN, false, false, true><<<grid, NT, lds, st>>>(P);
     }
-  }
-  if (multi) launch();
-  return 0;
-}
-
-int dl_conv_fwd(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, int osh, int osw,
-                int oh0, int ow0, long ldo, hipStream_t st, float* stats, long stat_rows, const DlBnBwdEpi* bn) {
-  const DlConvFwdJob job{g, w, ldw, oh0, ow0, stat_rows};
-  return dl_conv_fwd_multi(&job, 1, N, out, OH, OW, osh, osw, ldo, st, stats, bn);
-}
-
-// dl_conv_fwd with the inference epilogue (one job, no statistics): the same validation, variant
-// choice and grid as dl_conv_fwd_multi makes for that job, on the AFF instantiations
-int dl_conv_fwd_affine(const DlConvGeom& g, const bf16_t* w, long ldw, int N, bf16_t* out, int OH, int OW, long ldo,
-                       const float* scale, const float* shift, const bf16_t* res, int relu, hipStream_t st) {
-  if (N < 8 || N % 8 || ldo % 8 || !scale || !shift) return -1;
-  const bool sub = g.C < BK;
-  if ((sub ? (BK % g.C || g.C % 8) : g.C % BK) || ldw % 8 || g.I < 0 || g.J < 0) return -1;
-  if (sub && (g.TR * g.TS * g.C) % BK) return -1;
-  const long M = (long)g.Nimg * g.I * g.J;
-  if (M >= (1L << 24)) return -1;  // fdiv exactness bound (pixel decodes)
-  const long img_bytes = 2L * g.Nimg * g.H * g.W * g.C, w_bytes = 2L * N * ldw;
-  if (img_bytes >= (1L << 31) || w_bytes >= (1L << 31)) return -1;  // 32-bit buffer offsets
-  if (M == 0) return 0;
-  const bool narrow = N <= 64;
-  const int TMv = narrow ? 256 : BM, TNv = narrow ? 64 : BN;
-  const long tiles = ((M + TMv - 1) / TMv) * ((N + TNv - 1) / TNv);
-  if (tiles >= (1L << 31)) return -1;
-  static bool attr = false;
-  if (!attr) {
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN, false, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM + BN) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<256, 64, false, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<BM, BN, true, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (BM + BN) * 128));
-    DL_HIP_CHECK(hipFuncSetAttribute((const void*)conv_fwd_kernel<256, 64, true, false, true>,
-                                     hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (256 + 64) * 128));
-    attr = true;
-  }
-  const int tpw = (int)std::max<long>(1, tiles / DL_CONV_FWD_WG);
-  FwdAffine P{};
-  P.a[0] = FwdArgs{g, w, ldw, N, out, OH, OW, 1, 1, 0, 0, ldo, g.Nimg * g.I * g.J, g.TR * g.TS * g.C,
-                   (unsigned)img_bytes, (unsigned)w_bytes, tpw, nullptr, 0, DlBnBwdEpi{}, 0};
-  P.n = 1;
-  P.wg_begin[1] = (int)((tiles + tpw - 1) / tpw);
-  P.scale = scale;
-  P.shift = shift;
-  P.res = res;
-  P.relu = relu;
-  const dim3 grid(P.wg_begin[1]);
-  const int lds = 2 * (TMv + TNv) * 128;
-  if (sub) {
-    if (narrow) conv_fwd_kernel<256, 64, true, false, true><<<grid, NT, lds, st>>>(P);
-    else conv_fwd_kernel<BM, BN, true, false, true><<<grid, NT, lds, st>>>(P);
+  } else if (sub) {
+    if (narrow) conv_fwd_kernel<256, 64, true><<<grid, NT, lds, st>>>(P);
+    else conv_fwd_kernel<BM, BN, true><<<grid, NT, lds, st>>>(P);
   } else {
-    if (narrow) conv_fwd_kernel<256, 64, false, false, true><<<grid, NT, lds, st>>>(P);
-    else conv_fwd_kernel<BM, BN, false, false, true><<<grid, NT, lds, st>>>(P);
+    if (narrow) conv_fwd_kernel<256, 64><<<grid, NT, lds, st>>>(P);
+    else conv_fwd_kernel<BM, BN><<<grid, NT, lds, st>>>(P);
   }
   return 0;
 }
